@@ -21,7 +21,12 @@ Workloads (`--config`, named in config.workload):
              1 000 000 x 30) split over the ranks by cell block — strong scaling (c1 - c3 are single-GPU configs: a few
              microseconds of work per data set, bound by launches).
 
-N > 1: ONE line carries the whole scaling answer — `value` (permuted ids, in order, exchange chosen from the data), `pipelined`
+A plain run (`--gpus N --steps K --warmup W`) measures the headline only: it sets up, settles the clocks (`--pre-warm-ms`), runs the
+W warm-up steps, times the K steps, writes what the last step computed when `--dump-outputs DIR` is given, and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's description).  Everything else below —
+the roofline, the oracle check, the CPU baseline, the legs and the cumulative N > 1 lines — is a `--full` run's.
+
+`--full`, N > 1: ONE line carries the whole scaling answer — `value` (permuted ids, in order, exchange chosen from the data), `pipelined`
 (the same, overlapped), `spatial_ids` (ids with locality: the halo form, in order and overlapped, rows named outside the block),
 `peer` (the single-process form of the C ABI: every device pulls the other devices' table slices with hipMemcpyPeerAsync),
 `single_gpu_step` (rank 0 timing the N = 1 step in the same process, after the N-rank region) and `efficiency` (each of
@@ -63,6 +68,9 @@ JACCARD_BYTES_PER_EDGE = 28      # 4 B index entry read once + 24 B reference ou
 GFICF_BYTES_PER_NNZ = 24         # 4 (count pass rowidx) + 12 (scale pass rowidx+x) + 8 (write x)  
 GFICF_G, GFICF_N = 23_000, 54_000  # BASELINE config 3 shape (Tabula-Muris-sized synthetic stand-in)
 KNN_N, KNN_D, KNN_K = 100_000, 50, 31  # north-star point: 100 k cells, 50 PCA components, k = 30 + the cell itself
+DUMP_MAX_BYTES = 48 << 20        # --dump-outputs: the files of all ranks together stay under this (a seeded sample of rows beyond it)
+# options that only shape what a --full run measures besides the headline (refused without --full)
+FULL_ONLY = ("no_cpu_baseline", "no_gficf", "no_knn", "no_extras", "pipeline", "legs", "no_host_gficf", "no_peer", "no_chain", "no_live_traffic")
 
 
 def parse():
@@ -108,7 +116,22 @@ def parse():
                     help="N > 1: all-gather of every rank's table rows; halo: sub-problems in local ids, only the rows a block names travel "
                          "(fixed-capacity request slots, gficf_amd.dist.JaccardHaloShard); halo_generic: round 2's torch-side halo on global ids; "
                          "auto (default): halo when the warm-up step of data set 0 fits the request slots on every rank, all-gather otherwise")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the run from idle, the duplicate-scan figure, the roofline (live rocprofv3 passes), "
+                         "the oracle check and the further legs (--legs).  Without it a run sets up, warms up, times the K steps, writes "
+                         "--dump-outputs if asked and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64): every data set's rows of the "
+                         "(N*k) x 3 edge matrix, or a fixed seeded sample of them (the same rows for every data set; DIR/jaccard_rows.npy "
+                         f"names them) when they exceed {DUMP_MAX_BYTES >> 20} MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        full_only = [f"--{d.replace('_', '-')}" for d in FULL_ONLY if getattr(args, d) != ap.get_default(d)]
+        if full_only:
+            ap.error(f"{', '.join(full_only)}: shape(s) what only a --full run measures; add --full")
+    return args
 
 
 def time_kernel_ms(torch, fn, iters):
@@ -1098,7 +1121,7 @@ class Bench:
         N_total, k, batch, world, rank = self.N_total, self.k, self.batch, self.world, self.rank
         self.assert_same_format()
         self.progress("value: inputs")
-        self.idx_local, self.mat = self.make_inputs(a.ids, rank == 0)
+        self.idx_local, self.mat = self.make_inputs(a.ids, rank == 0 and a.full)     # (the full matrix of data set 0: oracle check, CPU baseline)
         self.progress("value: exchange form")
         self.exchange, self.named_outside = self.pick_exchange(self.idx_local[0], a.exchange)
         self.shards = self.make_shards(self.exchange, batch)
@@ -1120,7 +1143,7 @@ class Bench:
         # N = 1: the same W + K steps FROM IDLE first (what rounds 1-3 reported as `value`, and what one call from a cold R session
         # sees: the clocks are still ramping) ...
         value_from_idle = None
-        if world == 1 and a.pre_warm_ms > 0:
+        if a.full and world == 1 and a.pre_warm_ms > 0:
             dt_idle, _ = self.timed(step, a.steps, a.warmup)
             value_from_idle = self.edges_per_step * a.steps / dt_idle
         # ... then the clocks are settled, then W warm-up steps, then the K timed ones
@@ -1131,9 +1154,11 @@ class Bench:
         for sh in self.shards:
             sh.sync()                                                   # surfaces deferred validation errors
         self.value = value = self.edges_per_step * a.steps / dt
+        if a.dump_outputs:
+            self.dump_outputs(a.dump_outputs)
         # the same K steps with the ingest's own duplicate scan (the sequence of rounds 1-3, `--scan-dups`), for comparison
         value_scan = value
-        if self.distinct:
+        if a.full and self.distinct:
             ops.set_jaccard_distinct(False)
             dts, _ = self.timed(step, a.steps, 2)
             value_scan = self.edges_per_step * a.steps / dts
@@ -1166,12 +1191,37 @@ class Bench:
             "value_with_ingest_duplicate_scan": value_scan,
             "ms_per_data_set": dt / a.steps / batch * 1e3,
         })
+        if not a.full:                                                  # a plain run: the headline and what describes it, nothing measured besides
+            for key in ("value_from_idle", "value_from_idle_note", "value_with_ingest_duplicate_scan"):
+                del self.out[key]
+            return
         self.guard["t"] = time.monotonic()
         self.out["roofline"] = self.roofline()
         self.guard["t"] = time.monotonic()
         if world > 1:
             self.out["exchange"] = self.exchange_figures()
         self.oracle_check()
+
+    def dump_outputs(self, path):
+        """--dump-outputs: what the last timed step handed back — every data set's rows of this rank's slice of the (N*k) x 3 edge
+        matrix, as the caller receives it (float64: from, to, weight) — written to `path`/<name>.npy.  Beyond DUMP_MAX_BYTES (all ranks
+        together) a fixed sample of rows, seeded and therefore the same from run to run, stands for the whole: the same rows of every
+        data set, named (global 0-based row numbers) by jaccard_rows.npy.  N > 1: every rank writes its own files, prefixed rank<r>_."""
+        torch, k = self.torch, self.k
+        os.makedirs(path, exist_ok=True)
+        prefix = "" if self.world == 1 else f"rank{self.rank}_"
+        E = self.n_local * k
+        rows = min(E, (DUMP_MAX_BYTES // self.world) // (24 * self.batch + 8))
+        sel = None
+        if rows < E:
+            sel = np.sort(np.random.default_rng(20240).choice(E, size=rows, replace=False))
+            np.save(os.path.join(path, f"{prefix}jaccard_rows.npy"), (sel + self.b * k).astype(np.float64))
+            sel_dev = torch.from_numpy(sel).to(self.dev)
+        for d, sh in enumerate(self.shards):
+            out = sh.out if sel is None else sh.out.index_select(1, sel_dev)
+            np.save(os.path.join(path, f"{prefix}jaccard_set{d}.npy"), np.ascontiguousarray(out.t().cpu().numpy()))
+        self.out["dumped_outputs"] = {"dir": path, "data_sets": len(self.shards), "rows_per_data_set": rows, "of": E,
+                                      "kind": "all rows" if sel is None else "seeded sample of rows (jaccard_rows.npy)"}
 
     def one_launch_form(self):
         """Does the step of this workload take the one-launch form (small problem, one rank, distinct ids)?"""
@@ -1903,6 +1953,14 @@ def main():
     B.leg_value()
     B.leg_seconds["value"] = time.monotonic() - t0
     B.legs_done.append("value")
+    if not args.full:
+        # a plain run ends here: one line, on rank 0 (the legs below, and the cumulative N > 1 lines, are a --full run's)
+        if rank == 0 and not B.guard["done"]:
+            B.guard["done"] = True
+            print(B.line(), flush=True)
+        if world > 1:
+            B.dist.destroy_process_group()
+        return
     # N > 1: from here on the line holds `value`, its roofline, the exchange and the oracle check: printed NOW, and again after every leg
     B.progress()
     B.emit()

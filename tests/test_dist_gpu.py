@@ -138,7 +138,7 @@ def test_plain_bench_command_starts_its_own_ranks():
     env = dict(os.environ)
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
                         "--no-extras", "--cells-per-gpu", "8000"], capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -166,7 +166,7 @@ def test_bench_line_measures_the_edge_kernels_traffic_in_the_same_run():
     env = dict(os.environ)
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-gficf",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-gficf",
                         "--no-knn", "--batch", "2"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -281,7 +281,7 @@ def test_launcher_counts_the_gpus_of_this_box_from_sysfs_and_need_gpus_runs():
         env.pop(v, None)
     drv = ("import sys; sys.path.insert(0, %r)\nfrom gficf_amd import launch\n"
            "sys.exit(launch.spawn_ranks(sys.argv[1:], 1, need_gpus=1, timeout_s=250))\n" % ROOT)
-    r = subprocess.run([sys.executable, "-c", drv, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, "-c", drv, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras",
                         "--cells-per-gpu", "20000", "--pre-warm-ms", "0"], capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -301,7 +301,7 @@ def test_plain_multi_gpu_bench_line_carries_the_whole_scaling_answer():
     env = dict(os.environ)
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
                         "--cells-per-gpu", "8000", "--no-gficf", "--no-chain"], capture_output=True, text=True, timeout=580, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -337,13 +337,57 @@ def _bench_env():
     return env
 
 
+def test_plain_bench_run_is_the_headline_and_dumps_what_its_last_step_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one line with the headline (K timed steps, ms_per_step) and none of
+    the extras; `--dump-outputs DIR` writes every data set's rows of the edge matrix of the last step — all of them when they fit
+    (config 1), a seeded sample named by jaccard_rows.npy otherwise — equal to the oracle's rows of the same inputs, the same files
+    from run to run."""
+    import json
+    import subprocess
+
+    import oracle
+    from gficf_amd import synth
+
+    def run(out, *args):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)] + list(args), capture_output=True, text=True, timeout=280, env=_bench_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "c1", "--config", "c1")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["metric"] == "jaccard_edges_per_sec" and d["unit"] == "edges/s" and d["higher_is_better"] is True and d["dtype"] == "int32"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["legs_done"] == ["value"]
+    assert abs(d["value"] - d["config"]["edges_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "checked_vs_oracle", "value_from_idle", "value_with_ingest_duplicate_scan", "cpu_baseline", "gficf", "knn"):
+        assert key not in d, key
+    got = np.load(tmp_path / "c1" / "jaccard_set0.npy")
+    assert d["dumped_outputs"]["kind"] == "all rows" and sorted(os.listdir(tmp_path / "c1")) == ["jaccard_set0.npy"]
+    want, _ = oracle.jaccard(synth.knn_windowed(3000, 15, seed=42, perm_seed=43), nthreads=8)
+    assert got.dtype == np.float64 and np.array_equal(got, want)
+    # 100 k cells x k = 30, two data sets: 144 MB of rows, a sample of them
+    runs = [run(tmp_path / f"ns{i}", "--batch", "2", "--pre-warm-ms", "0") for i in (1, 2)]
+    files = sorted(os.listdir(tmp_path / "ns1"))
+    assert files == ["jaccard_rows.npy", "jaccard_set0.npy", "jaccard_set1.npy"] and runs[0]["dumped_outputs"]["rows_per_data_set"] < 3_000_000
+    assert sum(os.path.getsize(tmp_path / "ns1" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "ns1" / f), np.load(tmp_path / "ns2" / f)), f
+    rows = np.load(tmp_path / "ns1" / "jaccard_rows.npy").astype(np.int64)
+    for s in (0, 1):
+        want, _ = oracle.jaccard(synth.knn_windowed(100000, 30, seed=42 + 7 * s, perm_seed=43 + 7 * s), nthreads=min(16, os.cpu_count() or 8))
+        assert np.array_equal(np.load(tmp_path / "ns1" / f"jaccard_set{s}.npy"), want[rows]), s
+
+
 def test_bench_wall_budget_skips_and_names_the_legs_it_has_no_time_for():
     """`--budget-s`: a leg that would start with less than its reserve left is skipped on every rank alike and named in
     `skipped_legs`; `value` always runs; the run ends with code 0 and a whole line.  `--legs` selects."""
     import json
     import subprocess
 
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000", "--pre-warm-ms", "0",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000", "--pre-warm-ms", "0",
             "--no-gficf"]
     r = subprocess.run(base + ["--budget-s", "5"], capture_output=True, text=True, timeout=280, env=_bench_env())
     assert r.returncode == 0, r.stderr[-3000:]
@@ -366,7 +410,7 @@ def test_bench_killed_at_any_moment_after_its_first_line_leaves_a_whole_last_lin
     import subprocess
     import time
 
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000", "--pre-warm-ms", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000", "--pre-warm-ms", "0",
            "--no-gficf"]
     pr = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, env=_bench_env(), start_new_session=True)
     try:
@@ -394,7 +438,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks():
     import subprocess
 
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0",
+                        "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0",
                         "--cells-per-gpu", "6000", "--pre-warm-ms", "0", "--no-gficf", "--legs", "single_gpu_step"], capture_output=True, text=True, timeout=400, env=_bench_env())
     assert r.returncode == 0, r.stderr[-3000:]
     recs = [json.loads(l) for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
@@ -410,7 +454,7 @@ def test_bench_falls_back_to_gloo_and_says_so_when_rccl_cannot_build_its_communi
     import subprocess
 
     env = dict(_bench_env(), GFICF_BENCH_RANKS_SHARE_GPU0="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--cells-per-gpu", "6000",
                         "--pre-warm-ms", "0", "--no-extras"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.lstrip().startswith("{")][-1])

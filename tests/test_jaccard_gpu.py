@@ -502,7 +502,7 @@ def test_rccl_single_rank_collectives_and_bench_launch_path():
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29534", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--master-port", "29534", os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
                         "--no-cpu-baseline", "--no-gficf"], env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert r.returncode == 0 and '"metric": "jaccard_edges_per_sec"' in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 

@@ -73,7 +73,7 @@ def test_bench_self_launch_reaches_the_ranks_on_a_cpu_box():
     e = dict(os.environ)
     e.pop("WORLD_SIZE", None)
     e.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--no-extras"],
                        capture_output=True, text=True, timeout=240, env=e)
     assert r.returncode != 0 and "needs a GPU" in r.stderr and r.stdout.strip() == ""
 
@@ -104,3 +104,15 @@ def test_gpu_count_comes_from_sysfs_not_from_the_hip_runtime(tmp_path, monkeypat
     r = subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {ROOT!r}); import gficf_amd.launch as l; l.visible_gpus(); "
                         "print('torch' in sys.modules)"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "False", (r.stdout, r.stderr[-500:])
+
+
+def test_bench_options_of_a_full_run_are_refused_without_full():
+    """A plain `bench.py` run measures the headline only; the options that shape what a `--full` run adds are refused without
+    `--full` (exit 2, before anything is started), and `--steps` must be at least one timed step."""
+    for extra in (["--no-gficf"], ["--legs", "knn"], ["--no-extras"], ["--no-live-traffic"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "add --full" in r.stderr and extra[0] in r.stderr and r.stdout == "", (extra, r.stderr[-500:])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout

@@ -4,7 +4,8 @@
 RELAXED CONTRACT, stated here as include/gficf_hip.h states it: the reference is sequential and seed-exact, the device
 form is a deterministic parallel Louvain on the SAME objective.  What is tested:
   * against the reference's own outputs (tests/golden/louvain_cases.npz, made by running a build of the reference's
-    src/ModularityOptimizer.cpp; and the same binary live, oracle/_ref/, when it is there): modularity not more than
+    src/ModularityOptimizer.cpp; on the graphs built here, tests/golden/louvain_reference_runs.npz, and the same binary live,
+    oracle/_ref/, when it is there: tests/helpers/reference_runs.py): modularity not more than
     Q_TOL below the reference's, the same partition where the structure is unambiguous (planted partitions);
   * the modularity the call reports == the restated quality function (oracle_np.modularity_np, itself pinned to the
     reference's print-out) of the labels it returns, to 1e-9;
@@ -16,8 +17,8 @@ import pytest
 import scipy.sparse as sp
 
 import gficf_amd
-import oracle
 from oracle import oracle_np
+from tests.helpers import reference_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -70,16 +71,34 @@ def knn_graph(N, d, k, C, seed, spread=3.0):
     return gficf_amd.jaccard_adjacency(edges, N)
 
 
-@pytest.mark.parametrize("N,d,k,C,res", [(6000, 15, 15, 12, 0.8), (20000, 20, 30, 1, 0.8), (8000, 10, 50, 1, 1.0), (12000, 8, 10, 3, 2.0)])
+def hub_graph():
+    """Hubs with 3 000 and 30 000 neighbours, every leaf also on a ring (test_hub_vertices_beyond_the_table)."""
+    rng = np.random.default_rng(21)
+    N = 40000
+    rows, cols, vals = [], [], []
+    for hub, deg in ((0, 30000), (1, 3000)):
+        leaves = rng.choice(np.arange(2, N), deg, replace=False)
+        rows += [np.full(deg, hub)]; cols += [leaves]; vals += [rng.integers(1, 32, deg) / 64.0]
+    ring = np.arange(2, N)                                           # every leaf also sits on a ring: no isolated vertices
+    rows += [ring]; cols += [np.roll(ring, -1)]; vals += [np.full(N - 2, 0.5)]
+    W = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N)).tocsc()
+    A = (W + W.T).tocsc()
+    A.sum_duplicates(); A.sort_indices()
+    return A
+
+
+LIVE_CASES = [(6000, 15, 15, 12, 0.8), (20000, 20, 30, 1, 0.8), (8000, 10, 50, 1, 1.0), (12000, 8, 10, 3, 2.0)]
+FUNCTION2_CASES = [(6000, 15, 10, 0.05), (8000, 20, 1, 0.02)]
+
+
+@pytest.mark.parametrize("N,d,k,C,res", LIVE_CASES)
 def test_live_against_the_reference_binary(N, d, k, C, res):
     """The full chain on the device (kNN -> Jaccard -> filter -> adjacency -> Louvain) against the reference's optimiser run
     on the same adjacency matrix.  k = 50 and the structureless cases give vertices of degree > 128 (workgroup path)."""
-    if oracle.build_ref() is None:
-        pytest.skip("oracle/_ref/modularity_optimizer neither built nor buildable here")
     A = knn_graph(N, d, k, C, seed=N + k)
     lab = gficf_amd.run_modularity_clustering(A, 1, res, 1, 1, 10, 0, False)
     check_labels(A, lab, res)
-    ref_labels, printed = oracle.modularity_reference(A, res, 1, 1, 10, 0)
+    ref_labels, printed = reference_runs.modularity_reference(f"live_N{N}_d{d}_k{k}_C{C}_res{res}", A, res, 1, 1, 10, 0)
     q_ref = oracle_np.modularity_np(A, ref_labels, res)
     assert abs(q_ref - printed) < 6e-5
     assert lab.modularity >= q_ref - Q_TOL, (lab.modularity, q_ref)
@@ -89,20 +108,19 @@ def test_live_against_the_reference_binary(N, d, k, C, res):
 
 
 def test_large_graph_200k_cells_against_the_reference():
-    """200 k cells, k = 30 (9 M adjacency entries): label conventions, reported Q, reproducibility, and — when the reference
-    binary is there — its modularity on the same matrix (a few seconds on one core)."""
+    """200 k cells, k = 30 (9 M adjacency entries): label conventions, reported Q, reproducibility, and the reference's
+    modularity on the same matrix (its binary takes a few seconds on one core)."""
     A = knn_graph(200000, 20, 30, 40, seed=77, spread=2.0)
     lab = gficf_amd.run_modularity_clustering(A, 1, 0.8, 1, 1, 10, 0, False)
     check_labels(A, lab, 0.8)
     again = gficf_amd.run_modularity_clustering(A, 1, 0.8, 1, 1, 10, 0, False)
     assert np.array_equal(lab, again)
-    if oracle.build_ref() is not None:
-        ref_labels, printed = oracle.modularity_reference(A, 0.8, 1, 1, 10, 0)
-        q_ref = oracle_np.modularity_np(A, ref_labels, 0.8)
-        assert abs(q_ref - printed) < 6e-5 and lab.modularity >= q_ref - Q_TOL, (lab.modularity, q_ref)
+    ref_labels, printed = reference_runs.modularity_reference("large_200k", A, 0.8, 1, 1, 10, 0)
+    q_ref = oracle_np.modularity_np(A, ref_labels, 0.8)
+    assert abs(q_ref - printed) < 6e-5 and lab.modularity >= q_ref - Q_TOL, (lab.modularity, q_ref)
 
 
-@pytest.mark.parametrize("N,k,C,res", [(6000, 15, 10, 0.05), (8000, 20, 1, 0.02)])
+@pytest.mark.parametrize("N,k,C,res", FUNCTION2_CASES)
 def test_alternative_modularity_function(N, k, C, res):
     """RunModularityClustering(modularity = 2): unit node weights, the resolution taken as it is (reference
     src/RModularityOptimizer.cpp:36,100; never chosen by clustcells()).  Against the reference binary run with the same function."""
@@ -113,11 +131,10 @@ def test_alternative_modularity_function(N, k, C, res):
     assert lab.min() == 0 and (sizes > 0).all() and (np.diff(sizes) <= 0).all()
     std = gficf_amd.run_modularity_clustering(A, 1, 0.8, 1, 1, 10, 0, False)            # the context is back on the standard function
     assert abs(std.modularity - oracle_np.modularity_np(A, std, 0.8)) < 1e-9
-    if oracle.build_ref() is not None:
-        ref_labels, printed = oracle.modularity_reference(A, res, 1, 1, 10, 0, function=2)
-        q_ref = oracle_np.modularity_np(A, ref_labels, res, 2)
-        assert abs(q_ref - printed) < 6e-5                                              # the restatement vs the reference's print-out
-        assert lab.modularity >= q_ref - Q_TOL, (lab.modularity, q_ref)
+    ref_labels, printed = reference_runs.modularity_reference(f"function2_N{N}_k{k}_C{C}_res{res}", A, res, 1, 1, 10, 0, function=2)
+    q_ref = oracle_np.modularity_np(A, ref_labels, res, 2)
+    assert abs(q_ref - printed) < 6e-5                                                  # the restatement vs the reference's print-out
+    assert lab.modularity >= q_ref - Q_TOL, (lab.modularity, q_ref)
     with pytest.raises(ValueError):
         gficf_amd.run_modularity_clustering(A, 2, 1.5)
 
@@ -141,24 +158,13 @@ def test_ring_of_cliques_against_the_derived_partition_and_modularity(c, m, weig
 def test_hub_vertices_beyond_the_table():
     """Hubs with 3 000 and 30 000 neighbours, each neighbour its own community at the start: more than the 2048- and the
     8192-slot table hold — the second takes several passes over its edges.  Checked against the reference binary."""
-    rng = np.random.default_rng(21)
-    N = 40000
-    rows, cols, vals = [], [], []
-    for hub, deg in ((0, 30000), (1, 3000)):
-        leaves = rng.choice(np.arange(2, N), deg, replace=False)
-        rows += [np.full(deg, hub)]; cols += [leaves]; vals += [rng.integers(1, 32, deg) / 64.0]
-    ring = np.arange(2, N)                                           # every leaf also sits on a ring: no isolated vertices
-    rows += [ring]; cols += [np.roll(ring, -1)]; vals += [np.full(N - 2, 0.5)]
-    W = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N)).tocsc()
-    A = (W + W.T).tocsc()
-    A.sum_duplicates(); A.sort_indices()
+    A = hub_graph()
     lab = gficf_amd.run_modularity_clustering(A, 1, 1.0, 1, 1, 10, 0, False)
     check_labels(A, lab, 1.0)
     again = gficf_amd.run_modularity_clustering(A, 1, 1.0, 1, 1, 10, 0, False)
     assert np.array_equal(lab, again)
-    if oracle.build_ref() is not None:
-        ref_labels, _ = oracle.modularity_reference(A, 1.0, 1, 1, 10, 0)
-        assert lab.modularity >= oracle_np.modularity_np(A, ref_labels, 1.0) - Q_TOL
+    ref_labels, _ = reference_runs.modularity_reference("hubs", A, 1.0, 1, 1, 10, 0)
+    assert lab.modularity >= oracle_np.modularity_np(A, ref_labels, 1.0) - Q_TOL
 
 
 def test_resolution_and_iterations():
@@ -183,11 +189,10 @@ def test_resolution_and_iterations():
     assert refined.modularity >= one.modularity - 1e-12
     for lab, res in ((coarse, 0.3), (fine, 3.0), (one, 1.0), (ten, 1.0), (refined, 1.0)):
         check_labels(A, lab, res)
-    if oracle.build_ref() is not None:                                         # against the reference's algorithm 2
-        ref_labels, _ = oracle.modularity_reference(A, 1.0, 2, 1, 10, 0)
-        ref10 = gficf_amd.run_modularity_clustering(A, 1, 1.0, 2, 1, 10, 0, False)
-        check_labels(A, ref10, 1.0)
-        assert ref10.modularity >= oracle_np.modularity_np(A, ref_labels, 1.0) - Q_TOL
+    ref_labels, _ = reference_runs.modularity_reference("resolution_alg2", A, 1.0, 2, 1, 10, 0)      # against the reference's algorithm 2
+    ref10 = gficf_amd.run_modularity_clustering(A, 1, 1.0, 2, 1, 10, 0, False)
+    check_labels(A, ref10, 1.0)
+    assert ref10.modularity >= oracle_np.modularity_np(A, ref_labels, 1.0) - Q_TOL
 
 
 @pytest.mark.parametrize("N,k,C,res,alg,n_start", [(5000, 15, 1, 1.0, 1, 7), (9000, 30, 8, 0.8, 1, 10), (3000, 10, 1, 1.5, 2, 5), (7000, 50, 1, 1.0, 1, 20),

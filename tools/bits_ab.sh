@@ -6,7 +6,7 @@ TAG=${1:-r04}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 IDS=permuted
 run() { # name, env...
   name=$1_$IDS; shift
-  env "$@" timeout -k 10 200 python bench.py --config c4 --ids $IDS --no-cpu-baseline --no-live-traffic > $OUT/bench_c4_$name.json 2>> $OUT/bits_ab.err
+  env "$@" timeout -k 10 200 python bench.py --full --config c4 --ids $IDS --no-cpu-baseline --no-live-traffic > $OUT/bench_c4_$name.json 2>> $OUT/bits_ab.err
   python3 -c "
 import json; d=json.load(open('$OUT/bench_c4_$name.json')); r=d['roofline']
 print('%-26s value %.2f G edges/s  edges %.1f us in-run, %.1f back to back  ingest %.1f us  frac %.4f  row %d B  checked %s' % ('$name', d['value']/1e9, r['kernel_ms']*1e3, r['kernel_ms_back_to_back']*1e3, r['ingest_kernel_ms']*1e3, r['frac'], r['row_bytes'], d['checked_vs_oracle']))"

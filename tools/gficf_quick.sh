@@ -2,7 +2,7 @@
 # GF-ICF only: parity tests + pass time + per-kernel averages.  Usage: bash tools/gficf_quick.sh <tag>
 TAG=${1:-gq}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 timeout -k 10 400 python -m pytest tests/test_gficf_gpu.py -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/pytest.log
-timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-knn > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-knn > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 g=json.load(open("$OUT/bench.json"))["gficf"]; print("gficf %.4g cells/s  ms/pass %.4f  frac %.3f" % (g["value"], g["ms_per_pass"], g["roofline"]["frac"]))

@@ -11,11 +11,12 @@ TAG=${1:-r05}; PART=${2:-1}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
+ROOT=$PWD                     # the repository root (the profiled runs start from /tmp)
 if [ "$PART" = "1" ]; then
 timeout -k 10 500 python -m pytest tests -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
-(cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/trace -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-live-traffic > $GRAFT_REPO_ROOT/$OUT/bench_traced.json 2> $GRAFT_REPO_ROOT/$OUT/trace.log); echo "trace rc=$?"
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-400 $OUT/bench.json
+(cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/trace -o bench -- python3 $ROOT/bench.py --full --no-live-traffic > $ROOT/$OUT/bench_traced.json 2> $ROOT/$OUT/trace.log); echo "trace rc=$?"
 cp $(find $OUT/trace -name "bench_kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv && head -8 $OUT/bench_kernel_stats.csv | cut -c1-200
 CONFIGS_TO_TRACE="c1 c2 c3 c4 c5" bash tools/trace_configs.sh $TAG > $OUT/trace_configs.txt 2>&1; echo "trace configs rc=$?"
 timeout -k 10 200 python tools/halo_stage_times.py 1 2 4 8 > $OUT/halo_stage_times.jsonl 2>> $OUT/bench.err; echo "stage times rc=$?"
@@ -28,11 +29,11 @@ timeout -k 10 200 python tools/knn_prune_probe.py 2>&1 | grep -v amdgpu.ids > $O
 for SEED in 11 12 13; do timeout -k 10 150 python tools/fuzz_gpu.py 100 $SEED > $OUT/fuzz_seed$SEED.txt 2>&1; echo "fuzz seed $SEED rc=$?"; tail -2 $OUT/fuzz_seed$SEED.txt | cut -c1-300; done
 else
 S=$SECONDS
-timeout -k 10 420 python bench.py --gpus 3 --rehearse-one-gpu --steps 5 --no-gficf > $OUT/rehearsal_gpus3.jsonl 2> $OUT/rehearsal_gpus3.err; echo "rehearsal 3 ranks (full size) rc=$? in $((SECONDS-S)) s"
+timeout -k 10 420 python bench.py --full --gpus 3 --rehearse-one-gpu --steps 5 --no-gficf > $OUT/rehearsal_gpus3.jsonl 2> $OUT/rehearsal_gpus3.err; echo "rehearsal 3 ranks (full size) rc=$? in $((SECONDS-S)) s"
 S=$SECONDS
 # (five processes time-slicing ONE GPU over gloo: a data set takes ~1.5 s there, so this one runs 5 k cells per rank and 2 steps — and, with a
 # budget of 200 s, shows the budget doing its work: the legs it has no time for are skipped and named)
-timeout -k 10 420 python bench.py --gpus 5 --rehearse-one-gpu --steps 2 --warmup 1 --no-gficf --cells-per-gpu 5000 --budget-s 200 > $OUT/rehearsal_gpus5.jsonl 2> $OUT/rehearsal_gpus5.err; echo "rehearsal 5 ranks (5 k cells per rank, budget 200 s) rc=$? in $((SECONDS-S)) s"
+timeout -k 10 420 python bench.py --full --gpus 5 --rehearse-one-gpu --steps 2 --warmup 1 --no-gficf --cells-per-gpu 5000 --budget-s 200 > $OUT/rehearsal_gpus5.jsonl 2> $OUT/rehearsal_gpus5.err; echo "rehearsal 5 ranks (5 k cells per rank, budget 200 s) rc=$? in $((SECONDS-S)) s"
 for A in 3 5; do wc -l $OUT/rehearsal_gpus$A.jsonl; tail -1 $OUT/rehearsal_gpus$A.jsonl | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print({k: d.get(k) for k in ('legs_done','leg_seconds','skipped_legs','wall_s','checked_vs_oracle')})"; done
 bash tools/pmc_round.sh $TAG 2>&1 | tail -14
 timeout -k 10 200 python tools/fuzz_gpu.py 120 > $OUT/fuzz.txt 2>&1; echo "fuzz rc=$?"; tail -3 $OUT/fuzz.txt

@@ -3,7 +3,7 @@
 OUT=gpurun_out/${2:-ids_ab}; mkdir -p $OUT
 for sw in 0 1; do for c in north_star c4 c5; do for ids in permuted spatial; do
   export $1=$sw
-  python bench.py --config $c --ids $ids --no-extras --no-cpu-baseline --steps 10 > $OUT/$c.$ids.$sw.json 2> $OUT/$c.$ids.$sw.err || exit 1
+  python bench.py --full --config $c --ids $ids --no-extras --no-cpu-baseline --steps 10 > $OUT/$c.$ids.$sw.json 2> $OUT/$c.$ids.$sw.err || exit 1
 done; done; done
 python - <<PY
 import json,glob

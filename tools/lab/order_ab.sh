@@ -4,13 +4,13 @@
 OUT=gpurun_out/${1:-order_ab}; mkdir -p $OUT
 run() { # name env...
   local name=$1; shift
-  env "$@" python bench.py --config c5 --ids permuted --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.$name.json 2> $OUT/c5.$name.err || { tail -5 $OUT/c5.$name.err; exit 1; }
+  env "$@" python bench.py --full --config c5 --ids permuted --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.$name.json 2> $OUT/c5.$name.err || { tail -5 $OUT/c5.$name.err; exit 1; }
 }
 run off GFICF_JACCARD_ORDER=0
 run hops1 GFICF_JACCARD_ORDER_HOPS=1
 run hops2 GFICF_JACCARD_ORDER_HOPS=2
-env GFICF_JACCARD_ORDER_HOPS=1 python bench.py --config c5 --ids spatial --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.spatial_hops1.json 2> $OUT/c5.spatial_hops1.err
-env GFICF_JACCARD_ORDER=0 python bench.py --config c5 --ids spatial --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.spatial_off.json 2> $OUT/c5.spatial_off.err
+env GFICF_JACCARD_ORDER_HOPS=1 python bench.py --full --config c5 --ids spatial --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.spatial_hops1.json 2> $OUT/c5.spatial_hops1.err
+env GFICF_JACCARD_ORDER=0 python bench.py --full --config c5 --ids spatial --no-extras --no-cpu-baseline --steps 10 > $OUT/c5.spatial_off.json 2> $OUT/c5.spatial_off.err
 python - <<PY
 import json,glob
 for f in sorted(glob.glob("$OUT/c5.*.json")):

@@ -6,7 +6,8 @@ TAG=${1:-r06}; NAME=${2:-call}
 OUT=gpurun_out/$TAG/runs
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > $OUT/$NAME.json 2> $OUT/$NAME.err; echo "bench rc=$?"; cut -c1-300 $OUT/$NAME.json
-(cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/trace_$NAME -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-live-traffic > $GRAFT_REPO_ROOT/$OUT/${NAME}_traced.json 2> $GRAFT_REPO_ROOT/$OUT/${NAME}_trace.log); echo "trace rc=$?"
+ROOT=$PWD                     # the repository root (the profiled runs start from /tmp)
+timeout -k 10 400 python bench.py --full > $OUT/$NAME.json 2> $OUT/$NAME.err; echo "bench rc=$?"; cut -c1-300 $OUT/$NAME.json
+(cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/trace_$NAME -o bench -- python3 $ROOT/bench.py --full --no-live-traffic > $ROOT/$OUT/${NAME}_traced.json 2> $ROOT/$OUT/${NAME}_trace.log); echo "trace rc=$?"
 cp $(find $OUT/trace_$NAME -name "bench_kernel_stats.csv" | head -1) $OUT/${NAME}_kernel_stats.csv && head -4 $OUT/${NAME}_kernel_stats.csv | cut -c1-160
 rm -rf $OUT/trace_$NAME; find $OUT -name "*.db" -delete

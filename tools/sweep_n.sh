@@ -2,7 +2,7 @@
 # Usage: bash tools/sweep_n.sh k n1 n2 ...  -> bench (jaccard only) per cell count
 K=$1; shift
 for n in "$@"; do
-  timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-gficf --cells-per-gpu $n --k $K 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-gficf --cells-per-gpu $n --k $K 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 e=$n*$K

@@ -3,7 +3,7 @@
 OUT=gpurun_out/${1:-shapes}; mkdir -p $OUT
 for S in "10000 30" "54000 30" "100000 15" "100000 30" "100000 50" "100000 100" "1000000 15" "1000000 30"; do
   set -- $S
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --cells-per-gpu $1 --k $2 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline --cells-per-gpu $1 --k $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 e=$1*$2
