@@ -94,6 +94,19 @@ struct gficf_arena {
   T* at(size_t o) const { return reinterpret_cast<T*>(base + o); }
 };
 
+// Carving of a caller's workspace: take() the pieces in order (each 256 B aligned); base == nullptr only counts, total() is the size to ask for.
+struct gficf_carver {
+  char* base = nullptr;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (count * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+  size_t total() const { return off + 256; }
+};
+
 // banner lines of the host entries (the reference prints with Rprintf)
 void gficf_print(gficf_ctx* ctx, const char* line);
 
@@ -161,6 +174,19 @@ void gficf_set_error(const char* fmt, ...);
 
 __host__ __device__ static inline int64_t gficf_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// smallest b in 1..32 with 2^b > n: a value in [0, n] (an id in [0, n) and the marker n) fits b bits
+inline int gficf_bit_width(int64_t n) {
+  int b = 1;
+  while (b < 32 && ((int64_t)1 << b) <= n) ++b;
+  return b;
+}
+
+// the lanes of one wave see each other's LDS writes
+#define GFICF_WAVE_SYNC()                                                                                                                 \
+  do {                                                                                                                                    \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
+  } while (0)
+
 
 // ---------------------------------------------------------------- decoupled look-back over ticketed tiles (ctx->d_ws)
 // ws[0] is the ticket word (tiles are claimed in ticket order, so a tile's predecessors always belong to running
@@ -214,3 +240,10 @@ int gficf_ws_next_epoch(gficf_ctx* ctx, int64_t n_tiles, uint32_t* epoch);
 // In-place exclusive scan of n int64 values on the context's stream (scan.hip).
 // One launch (decoupled look-back); uses ctx->d_ws.  Sums must stay below 2^40.
 int gficf_exclusive_scan_i64(gficf_ctx* ctx, int64_t* d_data, int64_t n);
+
+// Stable radix sort of M elements key << 32 | value by the key's low b bits (radix_sort.hip), on the context's stream.  The elements
+// are read from kv0; key and value come out apart in okey / oval; kv0 and kv1 (M each) are both overwritten.  hist holds
+// gficf_radix_sort_hist_len(M', b) counts for any M' >= M.  M == 0: nothing is launched; b outside 1..32: GFICF_ERR_INVALID_ARG.
+int64_t gficf_radix_sort_hist_len(int64_t M, int b);
+int gficf_radix_sort_kv(gficf_ctx* ctx, unsigned long long* kv0, unsigned long long* kv1, int64_t* hist, int64_t M, int b, uint32_t* okey,
+                        uint32_t* oval);

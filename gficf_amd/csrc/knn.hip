@@ -36,8 +36,6 @@
 #include <type_traits>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <atomic>
 
 #include "common.h"
@@ -582,13 +580,15 @@ __global__ __launch_bounds__(256) void k_knn_iota(int32_t* __restrict__ v, int64
   if (e < n) v[e] = (int32_t)e;
 }
 
-// sort key of a point: (coarse pivot of its fine pivot) << 13 | fine pivot   (ids 1-based, at most 4096 fine pivots)
-__global__ __launch_bounds__(256) void k_knn_sort_keys(const int32_t* __restrict__ pivot_of, const int32_t* __restrict__ coarse_of,
-                                                       int64_t n, int32_t* __restrict__ keys) {
+// sort element of point e: key << 32 | e, key = (coarse pivot of its fine pivot - 1) << 12 | (fine pivot - 1)   (ids 1-based, at most
+// 4096 fine and 256 coarse pivots: 20 bits, two passes of the sort; stable, so the points of one cell keep the order of e)
+constexpr int KNN_CELL_KEY_BITS = 20;
+__global__ __launch_bounds__(256) void k_knn_sort_elems(const int32_t* __restrict__ pivot_of, const int32_t* __restrict__ coarse_of,
+                                                        int64_t n, u64* __restrict__ kv) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e < n) {
     const int32_t f = pivot_of[e];
-    keys[e] = (coarse_of[f - 1] << 13) | f;
+    kv[e] = ((u64)(uint32_t)(((coarse_of[f - 1] - 1) << 12) | (f - 1)) << 32) | (u64)e;
   }
 }
 
@@ -869,25 +869,16 @@ int knn_launch_m(gficf_ctx* ctx, int metric, const KnnTileArgs& a) {
   }
 }
 
-inline size_t knn_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t knn_sort_temp_bytes(int64_t n) {
-  size_t tmp = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, tmp, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, 0u, 32u,
-                                  (hipStream_t) nullptr);
-  return tmp;
-}
-
 // workspace of the pruned search, carved in this order.  Rows / tiles are counted with the padding of the cell-aligned
 // layout at its worst (every cell adds less than one tile).
 struct KnnPruneWs {
   int64_t C, xrows, qrows, n_ct, n_qt;      // pivots; padded candidate / query rows; candidate / query tiles (upper bounds)
   float *pivots, *coarse, *xp, *qp, *centers, *radius, *lb;
   u64* apart;                       // assignment: N lists of one key (also used for the pivots' own assignment)
-  int32_t *pivot_of, *coarse_of, *keys, *key_tmp, *iota, *perm_sorted, *perm_x, *perm_q, *cstart, *pstart, *tile_n, *qtile_n;
+  int32_t *pivot_of, *coarse_of, *key_tmp, *perm_sorted, *perm_x, *perm_q, *cstart, *pstart, *tile_n, *qtile_n;
   int64_t* rank;
-  void* sort_tmp;
-  size_t sort_tmp_bytes;
+  u64 *kv0, *kv1;                   // the cell sort: its elements (N each) and its digit counts
+  int64_t* hist;
   u64* part;
   u64* part_plain;                  // the plain search's partial lists (taken when the data does not prune)
   unsigned long long* counters;     // [0] zero-bound pairs, [1] pairs, [2] (as uint32) the choice flag
@@ -896,41 +887,39 @@ struct KnnPruneWs {
 
 KnnPruneWs knn_prune_ws(char* base, int64_t n_q, int64_t N, int dpad, int k) {
   KnnPruneWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += knn_align(bytes); return (void*)p; };
+  gficf_carver cv{base};
   const int64_t C = knn_pivots(N);
   w.C = C;
   w.n_ct = gficf_ceil_div(N, KNN_TC) + (C < N ? C : N);
   w.n_qt = gficf_ceil_div(n_q, KNN_TQ) + (C < n_q ? C : n_q);
   w.xrows = w.n_ct * KNN_TC;
   w.qrows = w.n_qt * KNN_TQ;
-  w.pivots = (float*)take((size_t)C * dpad * 4);
-  w.coarse = (float*)take((size_t)knn_coarse(C) * dpad * 4);
-  w.coarse_of = (int32_t*)take((size_t)C * 4);
-  w.keys = (int32_t*)take((size_t)N * 4);
-  w.xp = (float*)take((size_t)w.xrows * dpad * 4);
-  w.qp = (float*)take((size_t)w.qrows * dpad * 4);
-  w.centers = (float*)take((size_t)w.n_ct * dpad * 4);
-  w.radius = (float*)take((size_t)w.n_ct * 4);
-  w.lb = (float*)take((size_t)w.n_qt * w.n_ct * 4);
-  w.apart = (u64*)take((size_t)N * 8);
-  w.pivot_of = (int32_t*)take((size_t)N * 4);
-  w.key_tmp = (int32_t*)take((size_t)N * 4);
-  w.iota = (int32_t*)take((size_t)N * 4);
-  w.perm_sorted = (int32_t*)take((size_t)N * 4);
-  w.perm_x = (int32_t*)take((size_t)w.xrows * 4);
-  w.perm_q = (int32_t*)take((size_t)w.qrows * 4);
-  w.cstart = (int32_t*)take((size_t)(C + 2) * 4);
-  w.pstart = (int32_t*)take((size_t)(C + 2) * 4);
-  w.tile_n = (int32_t*)take((size_t)w.n_ct * 4);
-  w.qtile_n = (int32_t*)take((size_t)w.n_qt * 4);
-  w.rank = (int64_t*)take((size_t)(N + 1) * 8);
-  w.sort_tmp_bytes = knn_sort_temp_bytes(N);
-  w.sort_tmp = take(w.sort_tmp_bytes);
-  w.part = (u64*)take((size_t)w.qrows * (size_t)k * 8);
-  w.part_plain = (u64*)take((size_t)n_q * (size_t)KNN_MAX_SPLIT * (size_t)k * 8);
-  w.counters = (unsigned long long*)take(32);
-  w.total = off + 256;
+  w.pivots = cv.take<float>((size_t)C * dpad);
+  w.coarse = cv.take<float>((size_t)knn_coarse(C) * dpad);
+  w.coarse_of = cv.take<int32_t>((size_t)C);
+  w.xp = cv.take<float>((size_t)w.xrows * dpad);
+  w.qp = cv.take<float>((size_t)w.qrows * dpad);
+  w.centers = cv.take<float>((size_t)w.n_ct * dpad);
+  w.radius = cv.take<float>((size_t)w.n_ct);
+  w.lb = cv.take<float>((size_t)w.n_qt * w.n_ct);
+  w.apart = cv.take<u64>((size_t)N);
+  w.pivot_of = cv.take<int32_t>((size_t)N);
+  w.key_tmp = cv.take<int32_t>((size_t)N);
+  w.perm_sorted = cv.take<int32_t>((size_t)N);
+  w.perm_x = cv.take<int32_t>((size_t)w.xrows);
+  w.perm_q = cv.take<int32_t>((size_t)w.qrows);
+  w.cstart = cv.take<int32_t>((size_t)(C + 2));
+  w.pstart = cv.take<int32_t>((size_t)(C + 2));
+  w.tile_n = cv.take<int32_t>((size_t)w.n_ct);
+  w.qtile_n = cv.take<int32_t>((size_t)w.n_qt);
+  w.rank = cv.take<int64_t>((size_t)(N + 1));
+  w.kv0 = cv.take<u64>((size_t)N);
+  w.kv1 = cv.take<u64>((size_t)N);
+  w.hist = cv.take<int64_t>((size_t)gficf_radix_sort_hist_len(N, KNN_CELL_KEY_BITS));
+  w.part = cv.take<u64>((size_t)w.qrows * (size_t)k);
+  w.part_plain = cv.take<u64>((size_t)n_q * (size_t)KNN_MAX_SPLIT * (size_t)k);
+  w.counters = cv.take<unsigned long long>(4);
+  w.total = cv.total();
   return w;
 }
 
@@ -1020,17 +1009,16 @@ int gficf_knn_search_device(gficf_ctx* ctx, const float* d_points, int64_t N, in
   hipLaunchKernelGGL(k_knn_merge, blocks_for(C), dim3(256), 0, ctx->stream, w.apart, C, 1, 1, metric, (const int32_t*)nullptr, w.coarse_of, (float*)nullptr, C, (const uint32_t*)nullptr, 0u);
   // 2. candidates sorted by (coarse, fine) pivot (stable: ties keep index order) and laid out cell by cell, every cell
   //    starting on a tile boundary; the queries of this block likewise, with the query tile size
-  hipLaunchKernelGGL(k_knn_sort_keys, blocks_for(N), dim3(256), 0, ctx->stream, w.pivot_of, w.coarse_of, N, w.keys);
-  hipLaunchKernelGGL(k_knn_iota, blocks_for(N), dim3(256), 0, ctx->stream, w.iota, N);
   GFICF_HIP_CHECK(hipMemsetAsync(w.xp, 0, sizeof(float) * (size_t)w.xrows * dpad, ctx->stream));
   GFICF_HIP_CHECK(hipMemsetAsync(w.qp, 0, sizeof(float) * (size_t)w.qrows * dpad, ctx->stream));
   GFICF_HIP_CHECK(hipMemsetAsync(w.perm_x, 0xFF, sizeof(int32_t) * (size_t)w.xrows, ctx->stream));
   GFICF_HIP_CHECK(hipMemsetAsync(w.perm_q, 0xFF, sizeof(int32_t) * (size_t)w.qrows, ctx->stream));
-  auto layout = [&](const int32_t* keys_in, int64_t n, int T, const float* src, float* dst, int32_t* perm_pad, int64_t n_tiles, int32_t* tile_n) -> int {
-    size_t tb = w.sort_tmp_bytes;
-    GFICF_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, keys_in, w.key_tmp, w.iota, w.perm_sorted, (size_t)n, 0u, 26u, ctx->stream));
+  auto layout = [&](int64_t first, int64_t n, int T, const float* src, float* dst, int32_t* perm_pad, int64_t n_tiles, int32_t* tile_n) -> int {
+    hipLaunchKernelGGL(k_knn_sort_elems, blocks_for(n), dim3(256), 0, ctx->stream, w.pivot_of + first, w.coarse_of, n, w.kv0);
+    int r = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, n, KNN_CELL_KEY_BITS, (uint32_t*)w.key_tmp, (uint32_t*)w.perm_sorted);
+    if (r) return r;
     hipLaunchKernelGGL(k_knn_cell_heads, blocks_for(n + 1), dim3(256), 0, ctx->stream, w.key_tmp, n, w.rank);
-    int r = gficf_exclusive_scan_i64(ctx, w.rank, n + 1);
+    r = gficf_exclusive_scan_i64(ctx, w.rank, n + 1);
     if (r) return r;
     hipLaunchKernelGGL(k_knn_cell_starts, blocks_for(n + 1), dim3(256), 0, ctx->stream, w.key_tmp, w.rank, n, w.cstart);
     hipLaunchKernelGGL(k_knn_cell_offsets, dim3(1), dim3(1024), 0, ctx->stream, w.cstart, w.rank + n, T, w.pstart);
@@ -1040,9 +1028,9 @@ int gficf_knn_search_device(gficf_ctx* ctx, const float* d_points, int64_t N, in
     GFICF_HIP_CHECK(hipGetLastError());
     return GFICF_OK;
   };
-  rc = layout(w.keys, N, KNN_TC, d_points, w.xp, w.perm_x, w.n_ct, w.tile_n);
+  rc = layout(0, N, KNN_TC, d_points, w.xp, w.perm_x, w.n_ct, w.tile_n);
   if (rc) return rc;
-  rc = layout(w.keys + q_begin, n_q, KNN_TQ, d_points + q_begin * dpad, w.qp, w.perm_q, w.n_qt, w.qtile_n);
+  rc = layout(q_begin, n_q, KNN_TQ, d_points + q_begin * dpad, w.qp, w.perm_q, w.n_qt, w.qtile_n);
   if (rc) return rc;
   // 3. centre and radius of every candidate tile; bound of every (query tile, candidate tile) pair
   GFICF_HIP_CHECK(hipMemsetAsync(w.counters, 0, 32, ctx->stream));
@@ -1121,12 +1109,9 @@ int gficf_knn_pivot_order_device(gficf_ctx* ctx, const float* d_points, int64_t 
   rc = knn_launch_m<false>(ctx, metric, ac);
   if (rc) return rc;
   hipLaunchKernelGGL(k_knn_merge, blocks_for(C), dim3(256), 0, ctx->stream, w.apart, C, 1, 1, metric, (const int32_t*)nullptr, w.coarse_of, (float*)nullptr, C, (const uint32_t*)nullptr, 0u);
-  hipLaunchKernelGGL(k_knn_sort_keys, blocks_for(N), dim3(256), 0, ctx->stream, w.pivot_of, w.coarse_of, N, w.keys);
-  hipLaunchKernelGGL(k_knn_iota, blocks_for(N), dim3(256), 0, ctx->stream, w.iota, N);
-  size_t tb = w.sort_tmp_bytes;
-  GFICF_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys, w.key_tmp, w.iota, d_order, (size_t)N, 0u, 26u, ctx->stream));
+  hipLaunchKernelGGL(k_knn_sort_elems, blocks_for(N), dim3(256), 0, ctx->stream, w.pivot_of, w.coarse_of, N, w.kv0);
   GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  return gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, N, KNN_CELL_KEY_BITS, (uint32_t*)w.key_tmp, (uint32_t*)d_order);
 }
 
 int gficf_knn_host(gficf_ctx* ctx, const double* X, int64_t N, int d, int64_t ld, int k, int metric, int32_t* idx, double* dist) {

@@ -60,8 +60,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <vector>
 
 #include <atomic>
@@ -1367,13 +1365,13 @@ __global__ __launch_bounds__(256) void k_lv_count(int64_t n, int64_t C, const in
   }
 }
 
-__global__ __launch_bounds__(256) void k_lv_size_keys(int64_t C, int64_t n, const int32_t* __restrict__ cnt, u64* __restrict__ keys,
-                                                      u64* __restrict__ ids) {
+// sort element of cluster c: (n - its size) << 32 | c; sorted stably by the key, the clusters come out by decreasing size, ties by id
+__global__ __launch_bounds__(256) void k_lv_size_keys(int64_t C, int64_t n, const int32_t* __restrict__ cnt, u64* __restrict__ kv) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c < C) { keys[c] = ((u64)(n - cnt[c]) << 32) | (u64)c; ids[c] = (u64)c; }
+  if (c < C) kv[c] = ((u64)(n - cnt[c]) << 32) | (u64)c;
 }
 
-__global__ __launch_bounds__(256) void k_lv_rank(int64_t C, const u64* __restrict__ sorted_ids, int32_t* __restrict__ rank) {
+__global__ __launch_bounds__(256) void k_lv_rank(int64_t C, const uint32_t* __restrict__ sorted_ids, int32_t* __restrict__ rank) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p < C) rank[sorted_ids[p]] = (int32_t)p;
 }
@@ -1390,23 +1388,6 @@ __global__ __launch_bounds__(256) void k_lv_iota32(int64_t n, int32_t* __restric
 }
 
 // ---- host side
-struct Bump {
-  char* base; size_t off, cap;
-  template <typename T> T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;     // base == NULL: sizing only
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
-static size_t lv_sort_tmp_bytes(int64_t m) {
-  size_t tmp = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, tmp, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (size_t)(m > 0 ? m : 1), 0u, 64u,
-                                  (hipStream_t) nullptr);
-  return tmp;
-}
-
 struct LvLevel {          // a coarse graph's arrays (capacity: the union's entries)
   int64_t* beg; int64_t* end; int32_t* nbr; u64* wt; u64* kv; uint8_t* vcomp; int32_t* big;
 };
@@ -1417,8 +1398,7 @@ struct LvWs {
   int32_t *comm, *next, *snapc[2], *size, *snapS[2], *cur, *lab, *seedl, *tops, *best, *cnt, *rank, *mark_r, *mark_w;
   u64 *K, *snapK[2], *iw;
   int64_t* flag;            // n_union + 1 entries: the renumbering scan
-  u64 *keys_a, *vals_a, *keys_b, *vals_b;      // final numbering (N entries)
-  void* sort_tmp; size_t sort_tmp_bytes;
+  u64* skv[2]; int64_t* shist; uint32_t *skey, *sid;      // final numbering: the sort's elements, counts and output (N entries)
   LvParts pt;
   LvCtl* ctl;
   u64* scalars;             // [0] 2W, [5] largest weight
@@ -1426,7 +1406,7 @@ struct LvWs {
 
 // the workspace of B starts run together
 static size_t lv_carve(LvWs* w, void* base, int64_t N, int64_t nnz, int B) {
-  Bump b{(char*)base, 0, 0};
+  gficf_carver b{(char*)base};
   const size_t n = (size_t)(N > 0 ? N : 1), m = (size_t)(nnz > 0 ? nnz : 1);
   const size_t nu = n * (size_t)B, mu = m * (size_t)B;
   LvWs d;
@@ -1443,9 +1423,8 @@ static size_t lv_carve(LvWs* w, void* base, int64_t N, int64_t nnz, int B) {
   d.K = b.take<u64>(nu); d.iw = b.take<u64>(nu);
   d.mark_r = b.take<int32_t>(nu); d.mark_w = b.take<int32_t>(nu);
   d.flag = b.take<int64_t>(nu + 1);
-  d.keys_a = b.take<u64>(n); d.vals_a = b.take<u64>(n); d.keys_b = b.take<u64>(n); d.vals_b = b.take<u64>(n);
-  d.sort_tmp_bytes = lv_sort_tmp_bytes((int64_t)n);
-  d.sort_tmp = b.take<char>(d.sort_tmp_bytes);
+  d.skv[0] = b.take<u64>(n); d.skv[1] = b.take<u64>(n); d.skey = b.take<uint32_t>(n); d.sid = b.take<uint32_t>(n);
+  d.shist = b.take<int64_t>((size_t)gficf_radix_sort_hist_len((int64_t)n, gficf_bit_width(N)));
   d.pt.in_small = b.take<u64>((size_t)LV_GRID * LV_MAX_B); d.pt.in_mid = b.take<u64>((size_t)LV_GRID_BIG * LV_MAX_B);
   d.pt.in_large = b.take<u64>((size_t)LV_GRID_BIG * LV_MAX_B);
   for (int i = 0; i < 2; ++i) {
@@ -1456,7 +1435,7 @@ static size_t lv_carve(LvWs* w, void* base, int64_t N, int64_t nnz, int B) {
   d.ctl = b.take<LvCtl>(1);
   d.scalars = b.take<u64>(8);
   if (w) *w = d;
-  return b.off + 256;
+  return b.total();
 }
 
 static inline unsigned lv_blocks(int64_t n, int per) { return (unsigned)gficf_ceil_div(n > 0 ? n : 1, per); }
@@ -1808,10 +1787,10 @@ int gficf_louvain_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indptr, con
   const int64_t C = n_best;
   GFICF_HIP_CHECK(hipMemsetAsync(w.cnt, 0, sizeof(int32_t) * (size_t)C, st));
   hipLaunchKernelGGL(k_lv_count, dim3(lv_grid(N, 256, 1024)), dim3(256), 0, st, N, C, (const int32_t*)w.best, w.cnt);
-  hipLaunchKernelGGL(k_lv_size_keys, dim3(lv_blocks(C, 256)), dim3(256), 0, st, C, N, (const int32_t*)w.cnt, w.keys_a, w.vals_a);
-  size_t tb = w.sort_tmp_bytes;
-  GFICF_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys_a, w.keys_b, w.vals_a, w.vals_b, (size_t)C, 0u, 64u, st));
-  hipLaunchKernelGGL(k_lv_rank, dim3(lv_blocks(C, 256)), dim3(256), 0, st, C, (const u64*)w.vals_b, w.rank);
+  hipLaunchKernelGGL(k_lv_size_keys, dim3(lv_blocks(C, 256)), dim3(256), 0, st, C, N, (const int32_t*)w.cnt, w.skv[0]);
+  rc = gficf_radix_sort_kv(ctx, w.skv[0], w.skv[1], w.shist, C, gficf_bit_width(N), w.skey, w.sid);      // keys in [0, N]
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_lv_rank, dim3(lv_blocks(C, 256)), dim3(256), 0, st, C, (const uint32_t*)w.sid, w.rank);
   hipLaunchKernelGGL(k_lv_final, dim3(lv_blocks(N, 256)), dim3(256), 0, st, N, (const int32_t*)w.best, (const int32_t*)w.rank, d_labels);
   GFICF_HIP_CHECK(hipGetLastError());
   if (modularity) *modularity = q_best;

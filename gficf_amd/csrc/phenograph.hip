@@ -15,18 +15,6 @@
 
 namespace {
 
-// One grow-only block of the context's pool carved into the call's buffers (no allocation once the pool has grown).
-struct Carver {
-  char* base = nullptr;
-  size_t off = 0;
-  template <typename T> T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
 // ---- the Jaccard stage on cells renumbered by locality (round 5; OFF by default since round 6, GFICF_PHENOGRAPH_ORDER=1 turns it on).
 // Measured stage by stage in round 6 (profiles/r06_phenograph_order_ab.txt): the renumbering needs a pass of its own over the points
 // (every cell's nearest pivot: 10 ms at 1 M x 50) to save 0.4 ms in the edge kernel, and it hands the adjacency build sources that do
@@ -85,7 +73,7 @@ extern "C" int gficf_phenograph_host(gficf_ctx* ctx, const double* X, int64_t N,
   const size_t order_ws = ordered ? gficf_knn_workspace_bytes(ctx, N, N, 1) : 0;
   void *d_X, *d_P, *d_kws, *d_idx, *d_table, *d_u, *d_cptr, *d_e3, *d_aws, *d_indptr, *d_indices, *d_ax, *d_lab;
   void *d_order = nullptr, *d_inv = nullptr, *d_idx2 = nullptr;
-  Carver cv;
+  gficf_carver cv;                                     // one grow-only block of the context's pool (no allocation once the pool has grown)
   for (int pass = 0; pass < 2; ++pass) {               // pass 0 sizes the block, pass 1 hands the pointers out
     cv.off = 0;
     d_X = cv.take<double>((size_t)ld * (size_t)d);
@@ -108,7 +96,7 @@ extern "C" int gficf_phenograph_host(gficf_ctx* ctx, const double* X, int64_t N,
     }
     if (pass == 0) {
       void* blk = nullptr;
-      const hipError_t e0 = gficf_pool_get(ctx, 0, cv.off + 256, &blk);
+      const hipError_t e0 = gficf_pool_get(ctx, 0, cv.total(), &blk);
       if (e0 != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_phenograph_host: %s", hipGetErrorString(e0));
       cv.base = (char*)blk;
     }

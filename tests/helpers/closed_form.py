@@ -93,4 +93,6 @@ def ring_of_cliques(c, m, weight=1.0):
 
 
 def ring_of_cliques_modularity(c, m, resolution):
+    if c == 1:                                   # the ring's one edge closes on its own clique: all the weight is inside, Q = 1 - resolution
+        return 1.0 - resolution
     return m * (m - 1) / (m * (m - 1) + 2.0) - resolution / c

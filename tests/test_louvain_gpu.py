@@ -139,7 +139,8 @@ def test_alternative_modularity_function(N, k, C, res):
         gficf_amd.run_modularity_clustering(A, 2, 1.5)
 
 
-@pytest.mark.parametrize("c,m,weight,n_start", [(60, 10, 1.0, 1), (60, 10, 0.37, 10), (1000, 40, 1.0, 1), (1000, 40, 2.5, 10), (8, 5, 1.0, 10)])
+@pytest.mark.parametrize("c,m,weight,n_start", [(60, 10, 1.0, 1), (60, 10, 0.37, 10), (1000, 40, 1.0, 1), (1000, 40, 2.5, 10), (8, 5, 1.0, 10),
+                                                 (1, 6, 1.0, 3)])
 def test_ring_of_cliques_against_the_derived_partition_and_modularity(c, m, weight, n_start):
     """An answer by counting, no oracle and no reference binary in the loop (tests/helpers/closed_form.py): c cliques of m vertices on a ring, one
     edge between neighbours.  For c < resolution x (m (m - 1) + 2) the optimum is one community per clique and Q = m (m - 1) / (m (m - 1) + 2) -

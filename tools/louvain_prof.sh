@@ -8,7 +8,7 @@ python - <<PY
 import csv, re
 rows = []
 for r in csv.DictReader(open("$OUT/trace/t_kernel_stats.csv")):
-    m = re.search(r"(k_lv_[a-z_0-9]*|k_scan[a-z_0-9]*|radix[a-z_0-9_]*|onesweep[a-z_0-9_]*)", r["Name"])
+    m = re.search(r"(k_lv_[a-z_0-9]*|k_scan[a-z_0-9]*|k_rs_[a-z_0-9]*)", r["Name"])
     if m: rows.append((float(r["TotalDurationNs"]) / 1e3, m.group(1), int(r["Calls"]), float(r["AverageNs"]) / 1e3))
 for t, n, c, a in sorted(rows, reverse=True)[:16]: print("%-28s calls %5d total %9.1f us avg %8.1f us" % (n, c, t, a))
 print("sum %.1f us" % sum(r[0] for r in rows))

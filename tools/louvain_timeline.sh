@@ -13,7 +13,7 @@ rows.sort()
 # the calls: split at k_lv_fix (first kernel of a call)
 starts = [i for i, r in enumerate(rows) if "k_lv_fix" in r[2]]
 i0 = starts[-1]
-call = [r for r in rows[i0:] if "k_lv" in r[2] or "scan" in r[2] or "rocprim" in r[2] or "fill" in r[2].lower() or "copy" in r[2].lower()]
+call = [r for r in rows[i0:] if "k_lv" in r[2] or "scan" in r[2] or "k_rs_" in r[2] or "fill" in r[2].lower() or "copy" in r[2].lower()]
 t0, t1 = call[0][0], max(r[1] for r in call)
 busy = 0; cur_end = t0; gaps = []
 for s, e, n in call:
