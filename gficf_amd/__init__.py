@@ -9,6 +9,7 @@ from ._lib import GficfError, LIB_PATH  # noqa: F401
 from .api import (  # noqa: F401
     Context,
     MultiContext,
+    cluster_markers,
     cluster_signatures,
     clustcells,
     clustcells_graph,
@@ -16,6 +17,7 @@ from .api import (  # noqa: F401
     HipOps,
     default_context,
     device_count,
+    findClusterMarkers,
     gficf,
     gficf_with_weights,
     jaccard_adjacency,
@@ -24,7 +26,10 @@ from .api import (  # noqa: F401
     jaccard_edges,
     jaccard_expand,
     phenograph,
+    p_adjust_fdr,
     rcpp_parallel_jaccard_coef,
+    rcpp_parallel_WMU_test,
+    rcpp_WMU_test,
     run_modularity_clustering,
     transpose_gficf,
 )

@@ -558,6 +558,140 @@ def cluster_signatures(gficf_mat, cluster, ctx: Context | None = None):
     return out.T, uniq[order]
 
 
+
+# ------------------------------------------------------------------ marker genes (libgficf_markers.so)
+def _first_appearance_ids(cluster, N: int):
+    """Labels numbered in order of first appearance (``base::unique`` order): (int32 ids, the label list)."""
+    lab = np.asarray(cluster)
+    if lab.shape != (N,):
+        raise ValueError("cluster must hold one label per cell")
+    uniq, first, inv = np.unique(lab, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")
+    rank = np.empty_like(order)
+    rank[order] = np.arange(len(order))
+    return np.ascontiguousarray(rank[inv], dtype=np.int32), uniq[order]
+
+
+def cluster_markers(cpms_csc, cluster, ctx: Context | None = None):
+    """One-vs-rest Mann-Whitney U test of every gene for every cluster, the test inside ``findClusterMarkers()`` (reference
+    R/deGenes.R:43-48 -> ``rcpp_parallel_WMU_test(cpms[, in], cpms[, out])``), all clusters in one call.
+
+    ``cpms_csc``: genes x cells (scipy sparse); ``cluster``: one label per cell.  Returns ``(P, LFC, labels)``: G x C float64
+    p-values and log2 fold changes, column j for the j-th label in ``base::unique`` order (``labels``).  The arithmetic is
+    the reference's, quirks included (include/gficf_markers.h).
+    """
+    from . import _markers_lib
+
+    M, colptr, rowidx, x = _csc_parts(cpms_csc)
+    G, N = M.shape
+    ids, labels = _first_appearance_ids(cluster, N)
+    C = len(labels)
+    P = np.zeros((C, G), dtype=np.float64)                   # C-order (C, G) == column-major G x C
+    LFC = np.zeros((C, G), dtype=np.float64)
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_markers_lib.load().gficf_cluster_markers_host(ctx.handle, G, N, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x),
+                                                         _np_ptr(ids), C, _np_ptr(P), _np_ptr(LFC)))
+    return P.T, LFC.T, labels
+
+
+def rcpp_parallel_WMU_test(matX, matY, printOutput: bool = False, ctx: Context | None = None) -> np.ndarray:
+    """``rcpp_parallel_WMU_test(matX, matY, printOutput)`` (reference src/rcpp_parallel_mann_whitney.cpp:107-129): per row, the
+    Mann-Whitney U test of matX's row against matY's.  Returns G x 2: ``[p, log2FC]``."""
+    from . import _markers_lib
+
+    X = np.asfortranarray(matX, dtype=np.float64)
+    Y = np.asfortranarray(matY, dtype=np.float64)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+        raise ValueError("matX and matY must be matrices with the same number of rows")
+    G = X.shape[0]
+    out = np.zeros((2, G), dtype=np.float64)                # C-order (2, G) == column-major G x 2
+    if printOutput:
+        print("Running Parallell WM-U test...")
+    ctx = ctx or default_context()
+    check(_markers_lib.load().gficf_cluster_markers_dense_host(ctx.handle, G, X.shape[1], _np_ptr(X), Y.shape[1], _np_ptr(Y), _np_ptr(out)))
+    if printOutput:
+        print("Done!!")
+    return out.T
+
+
+def rcpp_WMU_test(M, idx1, idx2, ctx: Context | None = None) -> np.ndarray:
+    """``rcpp_WMU_test(M, idx1, idx2)`` (reference src/rcpp_mann_whitney.cpp): the same test between the columns ``idx1`` and
+    ``idx2`` of ``M`` (1-based, as the reference's ``subset()`` takes them).  Returns G x 2: ``[p, log2FC]``."""
+    M = np.asarray(M, dtype=np.float64)
+    i1 = np.asarray(idx1, dtype=np.int64) - 1
+    i2 = np.asarray(idx2, dtype=np.int64) - 1
+    if M.ndim != 2 or ((i1 < 0) | (i1 >= M.shape[1])).any() or ((i2 < 0) | (i2 >= M.shape[1])).any():
+        raise ValueError("idx1 / idx2 must be 1-based column indices of M")
+    return rcpp_parallel_WMU_test(M[:, i1], M[:, i2], False, ctx)
+
+
+def p_adjust_fdr(p) -> np.ndarray:
+    """R's ``p.adjust(p, method = "fdr")`` (Benjamini-Hochberg), in R's order of operations:
+    ``pmin(1, cummin(n / i * p[o]))[ro]`` with ``o = order(p, decreasing = TRUE)``."""
+    p = np.asarray(p, dtype=np.float64)
+    n = len(p)
+    if n == 0:
+        return p.copy()
+    i = np.arange(n, 0, -1, dtype=np.float64)
+    o = np.argsort(-p, kind="stable")
+    q = np.minimum(1.0, np.minimum.accumulate((n / i) * p[o]))
+    out = np.empty(n, dtype=np.float64)
+    out[o] = q
+    return out
+
+
+def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, cpms=None, ctx: Context | None = None) -> dict:
+    """``findClusterMarkers(data, nt, hvg, verbose)`` of the reference (R/deGenes.R:15-60): marker genes of every cluster, the
+    Mann-Whitney U test of each cluster against the rest on the device (``cluster_markers``), then the reference's R
+    post-processing: per cluster in ``unique`` order ``fdr = p.adjust(p, "fdr")``, keep ``fdr < .05 & log2FC > 0``, order by
+    fdr, ``rbind``; the whole table ordered by log2FC, decreasing (both orders stable).  ``data$de.genes`` becomes a
+    ``pandas.DataFrame`` with the columns ``ens, log2FC, p.value, fdr, cluster``.
+
+    ``cpms``: the normalised genes x cells matrix (rows as ``data["rawCounts"]``).  The edgeR rescale of the reference's
+    ``normCounts`` is not run here (as in :func:`gficf`): without ``cpms`` the raw counts are tested, with a warning.  Genes
+    with no non-zero cell are dropped first (``normCounts(doc_proportion_min = 0)``); the rest set BH's n.  ``hvg=True`` needs
+    the locfit fit of ``findVarGenes``, which is not provided: pass ``hvg=False``, or an array of the row indices to keep.
+    ``nt`` is accepted for signature compatibility.  ``ens`` holds ``data["genes"]`` of the kept rows (the stand-in for R's
+    rownames) or, without it, the row indices.
+    """
+    import pandas as pd
+    import scipy.sparse as sp
+
+    if data.get("community") is None:
+        raise ValueError("Please identify cluster first! Run clustcells function.")
+    if data.get("rawCounts") is None:
+        raise ValueError("No raw/normalized counts stored. You should have run gficf normalization with storeRaw = T")
+    if hvg is True:
+        raise NotImplementedError("hvg=True needs findVarGenes (locfit), which is not provided: pass hvg=False, or the row "
+                                  "indices of the genes to keep")
+    if cpms is None:
+        warnings.warn("findClusterMarkers: no cpms= given, the raw counts are tested (the edgeR rescale is not run here)", stacklevel=2)
+        cpms = data["rawCounts"]
+    M = sp.csr_matrix(cpms)
+    names = np.asarray(data["genes"]) if data.get("genes") is not None and len(data["genes"]) == M.shape[0] else np.arange(M.shape[0])
+    rows = np.arange(M.shape[0]) if hvg is False or hvg is None else np.asarray(hvg, dtype=np.int64)
+    M = M[rows]
+    keep = np.diff((M != 0).tocsr().indptr) > 0             # normCounts(doc_proportion_min = 0): rowSums(M != 0) > 0
+    rows, M = rows[keep], sp.csc_matrix(M[keep])
+    cl = data.get("cluster")
+    if cl is None:
+        cl = np.asarray(data["community"]).astype(str)
+    tsmessage("... Start identify marker genes", verbose=verbose)
+    P, LFC, labels = cluster_markers(M, cl, ctx)
+    parts = []
+    for j, lab in enumerate(labels):
+        fdr = p_adjust_fdr(P[:, j])
+        sel = np.flatnonzero((fdr < .05) & (LFC[:, j] > 0))
+        sel = sel[np.argsort(fdr[sel], kind="stable")]
+        parts.append(pd.DataFrame({"ens": names[rows[sel]], "log2FC": LFC[sel, j], "p.value": P[sel, j], "fdr": fdr[sel],
+                                   "cluster": np.repeat(lab, len(sel))}))
+    res = pd.concat(parts, ignore_index=True)
+    res = res.iloc[np.argsort(-res["log2FC"].to_numpy(), kind="stable")].reset_index(drop=True)
+    data["de.genes"] = res
+    return data
+
+
 def run_modularity_clustering(SNN, modularity: int = 1, resolution: float = 0.8, algorithm: int = 1, n_start: int = 10,
                               n_iter: int = 10, random_seed: int = 0, print_output: bool = False, ctx: Context | None = None):
     """``RunModularityClustering(SNN, modularity, resolution, algorithm, n.start, n.iter, random.seed, print.output)``
@@ -1094,6 +1228,28 @@ class HipOps:
         """out: (C, G) float64 == column-major G x C; cluster: int32 ids in [0, C)."""
         check(self.L.gficf_cluster_signatures_device(self._bind(), G, n_cells, _tptr(colptr), _tptr(rowidx), _tptr(x),
                                                      _tptr(cluster), int(C), _tptr(out)))
+
+    @staticmethod
+    def cluster_markers_workspace_bytes(G: int, N: int, nnz: int, C: int) -> int:
+        """Device scratch of ``cluster_markers`` (libgficf_markers.so)."""
+        from . import _markers_lib
+
+        return int(_markers_lib.load().gficf_cluster_markers_workspace_bytes(int(G), int(N), int(nnz), int(C)))
+
+    def cluster_markers(self, G, n_cells, colptr, rowidx, x, cluster, C, ws, p, lfc):
+        """Marker-gene test on device-resident tensors (colptr int64, rowidx int32, x float64, cluster int32 ids in [0, C),
+        ws uint8 of ``cluster_markers_workspace_bytes``); p, lfc: (C, G) float64 == column-major G x C.  Enqueues only: call
+        ``cluster_markers_sync(ws)`` to wait and to collect the deferred input errors."""
+        from . import _markers_lib
+
+        check(_markers_lib.load().gficf_cluster_markers_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x),
+                                                               int(rowidx.numel()), _tptr(cluster), int(C), _tptr(ws),
+                                                               int(ws.numel() * ws.element_size()), _tptr(p), _tptr(lfc)))
+
+    def cluster_markers_sync(self, ws):
+        from . import _markers_lib
+
+        check(_markers_lib.load().gficf_cluster_markers_sync(self._bind(), _tptr(ws)))
 
     def louvain_workspace_bytes(self, N: int, nnz: int, n_start: int = 1) -> int:
         """Device scratch of ``louvain``: with ``n_start`` given, enough for min(n_start, 16) starts to run together (one launch set)."""
