@@ -238,7 +238,8 @@ __device__ inline int64_t gficf_lookback_exclusive(unsigned long long* ws, int64
 int gficf_ws_next_epoch(gficf_ctx* ctx, int64_t n_tiles, uint32_t* epoch);
 
 // In-place exclusive scan of n int64 values on the context's stream (scan.hip).
-// One launch (decoupled look-back); uses ctx->d_ws.  Sums must stay below 2^40.
+// One launch (decoupled look-back); uses ctx->d_ws.  Sums must stay in [0, 2^40): a tile total or a running prefix outside that
+// raises GFICF_ST_BAD_CSC (GFICF_ERR_BAD_CSC at the next gficf_ctx_sync).  n beyond 131,071 tiles: GFICF_ERR_UNSUPPORTED.
 int gficf_exclusive_scan_i64(gficf_ctx* ctx, int64_t* d_data, int64_t n);
 
 // Stable radix sort of M elements key << 32 | value by the key's low b bits (radix_sort.hip), on the context's stream.  The elements

@@ -325,7 +325,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_lookback(int64_t* __restr
   if (threadIdx.x < 64) {
     if (threadIdx.x == 0 && (total < 0 || (total >> GFICF_LB_VALUE_BITS) != 0)) atomicOr(status, GFICF_ST_BAD_CSC);    // counts out of range
     const int64_t run = gficf_lookback_exclusive(ws, tile, (int64_t)gridDim.x, epoch, total);
-    if (threadIdx.x == 0) s_prefix = run;
+    if (threadIdx.x == 0) {
+      if (((run + total) >> GFICF_LB_VALUE_BITS) != 0) atomicOr(status, GFICF_ST_BAD_CSC);   // the running sum left the descriptors' 40 bits
+      s_prefix = run;
+    }
   }
   __syncthreads();
   ex += s_prefix;

@@ -31,13 +31,14 @@ constexpr int64_t MK_MAX_N = 2097151;     // Z^3 - Z (and so T) fits int64 for e
 constexpr uint32_t MK_ST_LABEL = 1u;      // a label outside [0, C)
 constexpr uint32_t MK_ST_EMPTY = 2u;      // a cluster without cells
 constexpr uint32_t MK_ST_VALUE = 4u;      // a NaN or infinite value
+constexpr int MK_FIXED_MIN_K = 64;        // below this scale a value's truncation can exceed 2^-64: the gene's sums go to f64 instead
 
 struct MkGene {                           // per-gene results of the walk
   int64_t neg, pos;                       // stored entries < 0 and > 0
   int64_t t3;                             // sum of t^3 - t over the non-zero tie groups
   int64_t ndist;                          // distinct non-zero values
   u64 s_lo, s_hi;                         // sum of all values, 128-bit fixed point, scale 2^k
-  int32_t k, pad;
+  int32_t k, f64;                         // f64: k < MK_FIXED_MIN_K, the accumulators hold f64 sums (cluster in lo, rest in hi)
 };
 
 __device__ inline u64 mk_key(double v) {
@@ -145,7 +146,12 @@ __device__ inline int64_t mk_wave_sum(int64_t v) {
 
 // accumulators of gene g, C wide: r2 (sum of 2 * rank over the cluster's non-zero entries), cnt (its non-zero entries),
 // s_lo / s_hi (its value sum, 128-bit fixed point); LDS: the workgroup's own copy, written out at the end; GLOBAL: rows g of
-// the G x C arrays themselves (zeroed by the caller)
+// the G x C arrays themselves (zeroed by the caller).
+// A gene whose largest |v| puts the scale k below MK_FIXED_MIN_K (|v| >= 2^(61 - nb): beyond 2^50 at 2000 cells, 2^39 at 2^21)
+// would lose its small values to the truncation.  Its value sums are taken in f64 instead: thread 0 adds the gene's entries in
+// sorted order (canonical: tied entries hold equal values) into lo[c], then writes each cluster's rest into hi[c] as the sum over
+// the clusters before it plus the sum over those after it (never total - cluster, which cancels when the cluster holds the huge
+// value).  Sequential, so only for such genes; every other gene keeps the integer path and its bits.
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, int64_t nnz, int32_t C, const int64_t* __restrict__ tptr, const u64* __restrict__ ks,
                                                  const uint32_t* __restrict__ cls, const int64_t* __restrict__ e, const uint32_t* __restrict__ gstart,
@@ -168,9 +174,11 @@ __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, i
     __syncthreads();
     const int64_t b = tptr[g], end = tptr[g + 1] < nnz ? tptr[g + 1] : nnz, nnz_g = end > b ? end - b : 0;
     int k = 0;
+    bool f64 = false;
     if (nnz_g > 0) {
       const double mx = fmax(fabs(mk_value(ks[b])), fabs(mk_value(ks[end - 1])));
       if (mx > 0.0) k = 125 - ilogb(mx) - nb;        // N < 2^nb: N * max|v| * 2^k < 2^126
+      f64 = mx > 0.0 && k < MK_FIXED_MIN_K;
     }
     int64_t neg = 0, pos = 0, t3 = 0, nd = 0;
     __int128 tot = 0;
@@ -184,9 +192,11 @@ __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, i
       if (c >= (uint32_t)C) continue;                      // a label outside [0, C): raised by k_mk_labels
       atomicAdd(&r2[c], (u64)(2 * pos0 + t + 1));
       atomicAdd(&cnt[c], 1ull);
-      const __int128 f = mk_fixed(v, k);
-      mk_add128(&lo[c], &hi[c], f);
-      tot += f;
+      if (!f64) {
+        const __int128 f = mk_fixed(v, k);
+        mk_add128(&lo[c], &hi[c], f);
+        tot += f;
+      }
       if (v < 0.0) ++neg; else ++pos;
       if (i == s) { t3 += t * t * t - t; ++nd; }
     }
@@ -205,6 +215,29 @@ __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, i
       mk_add128(&s_tot[0], &s_tot[1], (__int128)(((unsigned __int128)thi << 64) | tlo));
     }
     __syncthreads();
+    if (f64) {
+      if (threadIdx.x == 0) {
+        for (int64_t i0 = b; i0 < end; i0 += 8) {          // eight entries' loads in flight
+          u64 kk[8];
+          uint32_t cc[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const int64_t i = i0 + j < end ? i0 + j : end - 1; kk[j] = ks[i]; cc[j] = cls[i]; }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const double v = mk_value(kk[j]);
+            if (i0 + j < end && v != 0.0 && cc[j] < (uint32_t)C) lo[cc[j]] = (u64)__double_as_longlong(__longlong_as_double((long long)lo[cc[j]]) + v);
+          }
+        }
+        double run = 0.0;
+        for (int c = 0; c < C; ++c) { hi[c] = (u64)__double_as_longlong(run); run += __longlong_as_double((long long)lo[c]); }
+        run = 0.0;
+        for (int c = C - 1; c >= 0; --c) {
+          hi[c] = (u64)__double_as_longlong(__longlong_as_double((long long)hi[c]) + run);
+          run += __longlong_as_double((long long)lo[c]);
+        }
+      }
+      __syncthreads();
+    }
     if (LDS)
       for (int t = threadIdx.x; t < C; t += 256) {
         a_r2[g * C + t] = r2[t]; a_cnt[g * C + t] = cnt[t]; a_lo[g * C + t] = lo[t]; a_hi[g * C + t] = hi[t];
@@ -212,7 +245,7 @@ __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, i
     if (threadIdx.x == 0) {
       MkGene o;
       o.neg = s_red[0]; o.pos = s_red[1]; o.t3 = s_red[2]; o.ndist = s_red[3];
-      o.s_lo = s_tot[0]; o.s_hi = s_tot[1]; o.k = k; o.pad = 0;
+      o.s_lo = s_tot[0]; o.s_hi = s_tot[1]; o.k = k; o.f64 = f64 ? 1 : 0;
       gst[g] = o;
     }
     __syncthreads();                                       // LDS reused by the next gene
@@ -251,10 +284,12 @@ __global__ __launch_bounds__(256) void k_mk_epilogue(int64_t G, int64_t N, int32
       z = z / sig;
       p = erfc(fabs(z) / 1.4142135623730951);
     }
-    // log2(avg(v1 + 1) / avg(v2 + 1)); the rest's sum = the gene's total - the cluster's, exact in fixed point
+    // log2(avg(v1 + 1) / avg(v2 + 1)); the rest's sum = the gene's total - the cluster's, exact in fixed point (f64 genes: both
+    // sums as the walk left them)
     const u64 clo = a_lo[a], chi = a_hi[a];
     const u64 rlo = s.s_lo - clo, rhi = s.s_hi - chi - (s.s_lo < clo ? 1ull : 0ull);
-    const double sc = mk_fixed_to_double(clo, chi, s.k), sr = mk_fixed_to_double(rlo, rhi, s.k);
+    const double sc = s.f64 ? __longlong_as_double((long long)clo) : mk_fixed_to_double(clo, chi, s.k);
+    const double sr = s.f64 ? __longlong_as_double((long long)chi) : mk_fixed_to_double(rlo, rhi, s.k);
     p_out[q] = p;
     lfc_out[q] = log2(((sc + (double)n1) / (double)n1) / ((sr + (double)n2) / (double)n2));
   }

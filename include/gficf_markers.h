@@ -19,7 +19,10 @@
  *     distinct value;
  *   - log2FC = log2(((S_c + n1) / n1) / ((S_rest + n2) / n2)), S = sum of the values (the reference's avg(v + 1)); the sums are
  *     accumulated as 128-bit fixed-point integers, so the result does not depend on the order of the additions: the same input
- *     gives the same bits on every call, and permuting the cells together with their labels changes nothing.
+ *     gives the same bits on every call, and permuting the cells together with their labels changes nothing.  A gene whose
+ *     largest |value| would push the fixed-point scale below 2^64 (|v| >= 2^(61 - bit_width(N))) sums in f64 instead, in its
+ *     sorted order and with the rest's sum built without subtraction: as accurate as the reference's f64 sums, just as
+ *     deterministic, and slower (one thread walks such a gene).
  * Rejected: a NaN or infinite value (GFICF_ERR_BAD_VALUE), C < 2, an empty cluster, a label outside [0, C)
  * (GFICF_ERR_INVALID_ARG), a malformed CSC (GFICF_ERR_BAD_CSC).
  * Outputs are G x C, column-major f64: column c belongs to label c (callers number labels in base::unique order). */

@@ -1,0 +1,86 @@
+"""Builds tests/helpers/prim_probe.hip against gficf_amd/csrc/common.h into tests/helpers/libprim_probe.so (linked to
+libgficf_hip.so) and binds it with ctypes: the radix sort, the int64 exclusive scan and the scan epoch of a context, which
+the library keeps internal (the exported gficf_* surface is pinned by tests/test_abi.py).  Test infrastructure only."""
+from __future__ import annotations
+
+import ctypes
+import os
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.join(ROOT, "tests", "helpers")
+SRC = os.path.join(HERE, "prim_probe.hip")
+SO = os.path.join(HERE, "libprim_probe.so")
+LIBDIR = os.path.join(ROOT, "gficf_amd")
+CSRC = os.path.join(LIBDIR, "csrc")
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "gficf_hip.h")]
+
+SYMBOLS = ["probe_radix_sort_kv", "probe_radix_sort_hist_len", "probe_exclusive_scan_i64", "probe_get_scan_epoch",
+           "probe_set_scan_epoch", "probe_ctx_sync"]
+
+
+def hipcc() -> str | None:
+    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
+        if c and os.path.exists(c):
+            return c
+    return None
+
+
+def build(force: bool = False) -> str:
+    """Compile the probe (gfx950) unless an up-to-date build is there; returns the path of the shared object."""
+    cc = hipcc()
+    if cc is None:
+        raise RuntimeError("hipcc not found")
+    lib = os.path.join(LIBDIR, "libgficf_hip.so")
+    if not os.path.exists(lib):
+        raise RuntimeError("gficf_amd/libgficf_hip.so is missing: run __graft_entry__.build() first")
+    newest = max(os.path.getmtime(f) for f in [SRC, lib] + HEADERS)
+    if force or not os.path.exists(SO) or os.path.getmtime(SO) < newest:
+        tmp = SO + ".tmp%d" % os.getpid()
+        cmd = [cc, "-O2", "-std=c++17", "--offload-arch=gfx950", "-shared", "-fPIC", "-Wall", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+               SRC, "-L", LIBDIR, "-lgficf_hip", "-Wl,-rpath," + LIBDIR, "-o", tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            raise RuntimeError("building the primitive probe failed:\n" + r.stderr[-3000:])
+        os.replace(tmp, SO)
+    return SO
+
+
+class Probe:
+    def __init__(self):
+        import torch  # noqa: F401  (one HIP runtime in the process, as gficf_amd/_lib.py has it)
+
+        from gficf_amd import _lib
+
+        _lib.load()
+        self.L = L = ctypes.CDLL(build())
+        vp, i64, ci, u32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32
+        for name, res, args in [
+            ("probe_radix_sort_kv", ci, [vp, vp, vp, vp, i64, ci, vp, vp]),
+            ("probe_radix_sort_hist_len", i64, [i64, ci]),
+            ("probe_exclusive_scan_i64", ci, [vp, vp, i64]),
+            ("probe_get_scan_epoch", u32, [vp]),
+            ("probe_set_scan_epoch", None, [vp, u32]),
+            ("probe_ctx_sync", ci, [vp]),
+        ]:
+            f = getattr(L, name)
+            f.restype, f.argtypes = res, args
+
+    def sort_kv(self, ctx, kv0, kv1, hist, M, b, okey, oval) -> int:
+        return self.L.probe_radix_sort_kv(ctx, kv0, kv1, hist, int(M), int(b), okey, oval)
+
+    def hist_len(self, M, b) -> int:
+        return int(self.L.probe_radix_sort_hist_len(int(M), int(b)))
+
+    def scan(self, ctx, d, n) -> int:
+        return self.L.probe_exclusive_scan_i64(ctx, d, int(n))
+
+    def epoch(self, ctx) -> int:
+        return int(self.L.probe_get_scan_epoch(ctx))
+
+    def set_epoch(self, ctx, e: int):
+        self.L.probe_set_scan_epoch(ctx, int(e))
+
+    def sync(self, ctx) -> int:
+        return self.L.probe_ctx_sync(ctx)

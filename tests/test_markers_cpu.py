@@ -42,6 +42,79 @@ def test_literal_and_shared_sort_forms_agree(kind):
     assert (a["p"][1] == 1.0).all()
 
 
+@pytest.mark.parametrize("kind", ["counts", "cpm", "signed", "explicit_zeros", "one_value"])
+def test_sparse_oracle_equals_the_shared_sort_and_literal_forms(kind):
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng({"counts": 21, "cpm": 22, "signed": 23, "explicit_zeros": 24, "one_value": 25}[kind])
+    G, N, C = 14, 73, 5
+    D = rng.poisson(0.8, (G, N)).astype(np.float64)
+    if kind == "cpm":
+        D = D / np.maximum(D.sum(0), 1) * 1e6
+    if kind == "signed":
+        D[rng.random((G, N)) < 0.25] *= -1.5
+        D[0, :6] = -0.0
+    D[1] = 3.0                                           # one distinct value, no zero
+    D[2] = 0.0                                           # all zero
+    D[3, :N - 2] = 0.0                                   # nearly all zero
+    if kind == "one_value":
+        D[D != 0] = 2.5
+    S = sp.csc_matrix(D)
+    if kind in ("explicit_zeros", "signed"):             # stored zeros (and -0.0) next to the non-zeros
+        coo = S.tocoo()
+        zr, zc = np.nonzero(D == 0)
+        pick = rng.random(len(zr)) < 0.3
+        zv = np.where(np.arange(pick.sum()) % 2 == 0, 0.0, -0.0)
+        S = sp.csc_matrix((np.concatenate([coo.data, zv]), (np.concatenate([coo.row, zr[pick]]), np.concatenate([coo.col, zc[pick]]))),
+                          shape=(G, N))
+        assert S.nnz > np.count_nonzero(D)
+    ids = _labels(rng, N, C)
+    a = mk.markers_literal(D, ids, C)
+    b = mk.markers_shared(S, ids, C)
+    c = mk.markers_sparse(S, ids, C)
+    for ref in (a, b):
+        for k in ("U1", "U2", "T", "p"):
+            assert np.array_equal(ref[k], c[k]), k
+        assert np.array_equal(np.isnan(ref["z"]), np.isnan(c["z"]))
+        assert np.array_equal(ref["z"][~np.isnan(ref["z"])], c["z"][~np.isnan(c["z"])])
+        assert np.allclose(ref["lfc"], c["lfc"], rtol=0, atol=1e-12)
+    assert (c["p"][1] == 1.0).all() and (c["p"][2] == 1.0).all()
+
+
+def test_sparse_oracle_at_scale_and_on_wide_ranges():
+    """A million genes in seconds; the rest's sum never cancels (a cluster holding a huge value); T near 2^63."""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(26)
+    G, N = 1_000_000, 40
+    nnz = 2_000_000
+    S = sp.csc_matrix((rng.integers(1, 5, nnz).astype(np.float64), (rng.integers(0, G, nnz), rng.integers(0, N, nnz))), shape=(G, N))
+    S.sum_duplicates()
+    ids = _labels(rng, N, 3)
+    r = mk.markers_sparse(S, ids, 3)
+    for g in (0, 17, G - 1):
+        w = mk.markers_shared(S[g], ids, 3)
+        for k in ("U1", "U2", "T", "p"):
+            assert np.array_equal(w[k][0], r[k][g]), k
+    N = 1000
+    row = rng.random(N) * 3
+    row[7] = 1e40
+    ids = _labels(rng, N, 4)
+    r = mk.markers_sparse(sp.csc_matrix(row[None, :]), ids, 4)
+    for c in range(4):
+        s1, s2 = math.fsum(row[ids == c]), math.fsum(row[ids != c])
+        n1 = int((ids == c).sum())
+        assert r["lfc"][0, c] == pytest.approx(math.log2(((s1 + n1) / n1) / ((s2 + N - n1) / (N - n1))), abs=1e-12)
+    N = 2_097_151
+    row = np.full(N, 2.0)
+    row[:3] = [0.0, 1.0, 5.0]
+    ids = np.zeros(N, dtype=np.int64)
+    ids[5] = 1
+    r = mk.markers_sparse(sp.csc_matrix(row[None, :]), ids, 2)
+    t = N - 3
+    assert r["T"][0, 0] == (t ** 3 - t) and r["T"][0, 0] > 2 ** 62
+
+
 def test_oracle_matches_scipy_where_the_quirks_do_not_apply():
     stats = pytest.importorskip("scipy.stats")
     rng = np.random.default_rng(5)

@@ -241,3 +241,193 @@ def test_find_cluster_markers_end_to_end():
     assert (df.loc[df["cluster"] == labels[fa[boost][0]], "ens"] < 1020).any()
     with pytest.warns(UserWarning, match="raw counts"):
         gficf_amd.findClusterMarkers(dict(data), hvg=False, verbose=False)
+
+
+# ------------------------------------------------------------------------------------------------ at scale and at every switch point
+def _config3_like(G, N, nnz, seed):
+    """genes x cells CPM matrix with about nnz stored entries (Zipf-like gene popularity, counts 1 + geometric)."""
+    rng = np.random.default_rng(seed)
+    w = 1.0 / np.arange(1, G + 1) ** 0.6
+    gene = rng.choice(G, nnz, p=w / w.sum())
+    cell = rng.integers(0, N, nnz)
+    lin = np.unique(cell.astype(np.int64) * G + gene)
+    c, g = lin // G, (lin % G).astype(np.int32)
+    cnt = (1 + rng.geometric(0.5, len(lin))).astype(np.float64)
+    colsum = np.bincount(c, weights=cnt, minlength=N)
+    x = cnt / colsum[c] * 1e6
+    colptr = np.concatenate([[0], np.cumsum(np.bincount(c, minlength=N))]).astype(np.int64)
+    return sp.csc_matrix((x, g, colptr), shape=(G, N))
+
+
+def _uneven_labels(seed, N, C):
+    rng = np.random.default_rng(seed)
+    w = rng.pareto(1.2, C) + 0.05
+    sizes = np.maximum(1, np.floor(w / w.sum() * (N - C))).astype(np.int64) + 0
+    sizes[np.argmax(sizes)] += N - sizes.sum()
+    return _labels(seed, N, C, sizes)
+
+
+@pytest.fixture(scope="module")
+def config3():
+    return _config3_like(23_000, 54_000, 10_800_000, seed=31)
+
+
+def test_config3_scale_ten_million_entries(config3):
+    """23 k genes (plain transpose, one gene range), 54 k cells, 45 uneven clusters: the three b = 32 / 15-bit sorts walk
+    several tiles per workgroup and the gene sort takes two passes."""
+    M = config3
+    assert M.nnz >= 10_000_000
+    ids = _uneven_labels(32, M.shape[1], 45)
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    _check(P, LFC, labels, mk.markers_sparse(M, ids, 45))
+
+
+@pytest.mark.parametrize("C", [2048, 2049])
+def test_lds_and_global_accumulators_at_the_switch(config3, C):
+    """C = 2048: 64 KiB of LDS accumulators (+ 48 B) a workgroup; 2049: global ones.  G * C > 16384 * 256: the epilogue
+    grid-strides."""
+    M = config3[:2600]
+    assert M.shape[0] * C > 16384 * 256
+    ids = _uneven_labels(33, M.shape[1], C)
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    _check(P, LFC, labels, mk.markers_sparse(M, ids, C))
+
+
+def test_million_genes_walk_grid_strides():
+    """1.1 M genes x 64 cells: a 21-bit gene sort in three passes, more genes than walk workgroups (2^20), 30 gene ranges of
+    the transpose."""
+    G, N = 1_100_000, 64
+    rng = np.random.default_rng(34)
+    nnz = 3_000_000
+    M = sp.csc_matrix((rng.integers(1, 6, nnz).astype(np.float64) * 0.5, (rng.integers(0, G, nnz), rng.integers(0, N, nnz))), shape=(G, N))
+    M.sum_duplicates()
+    ids = _labels(35, N, 3)
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    _check(P, LFC, labels, mk.markers_sparse(M, ids, 3))
+
+
+MK_MAX_N = 2_097_151
+
+
+def test_largest_n_tie_sums_near_two_to_the_63():
+    N = MK_MAX_N
+    rng = np.random.default_rng(36)
+    rows = np.zeros((4, N))
+    rows[0] = 7.25                                        # one tie group of N - 4 cells: t^3 - t close to 2^63
+    rows[0, [11, 500, N - 3, N - 1]] = [0.0, 1.0, 9.0, -2.0]
+    rows[1, rng.choice(N, 3, replace=False)] = [4.0, 4.0, -1.0]      # nearly all zero: Z^3 - Z close to 2^63
+    rows[2] = rng.permutation(N) + 0.5                    # all distinct
+    rows[3] = np.where(rng.random(N) < 0.4, 1.5, 3.0)     # two tie groups
+    M = sp.csc_matrix(rows)
+    ids = np.zeros(N, dtype=np.int32)
+    ids[rng.integers(0, N)] = 1                           # a cluster of one cell: n1 * n2 odd
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    ref = mk.markers_sparse(M, ids, 2)
+    assert ref["T"][0, 0] > 2 ** 62 and ref["T"][1, 0] > 2 ** 62
+    _check(P, LFC, labels, ref)
+
+
+def test_one_cell_more_than_the_largest_n_is_rejected_before_allocating():
+    L = _markers_lib.load()
+    N = MK_MAX_N + 1
+    ctx = gficf_amd.api.Context(0)                        # empty pools: an allocation would show in the free memory
+    try:
+        torch = pytest.importorskip("torch")
+        colptr = np.zeros(N + 1, dtype=np.int64)
+        cl = (np.arange(N) % 2).astype(np.int32)
+        p, l = np.zeros(2), np.zeros(2)
+        free0 = torch.cuda.mem_get_info(0)[0]
+        rc = L.gficf_cluster_markers_host(ctx.handle, 1, N, _np_ptr(colptr), 1, None, None, _np_ptr(cl), 2, _np_ptr(p), _np_ptr(l))
+        assert rc == 6                                    # GFICF_ERR_UNSUPPORTED
+        X, Y = np.zeros((1, N // 2)), np.zeros((1, N - N // 2))
+        out = np.zeros(2)
+        assert L.gficf_cluster_markers_dense_host(ctx.handle, 1, X.shape[1], _np_ptr(X), Y.shape[1], _np_ptr(Y), _np_ptr(out)) == 6
+        assert free0 - torch.cuda.mem_get_info(0)[0] < 4 << 20
+        assert L.gficf_cluster_markers_workspace_bytes(1, N, 0, 2) > 0
+    finally:
+        ctx.close()
+
+
+# values far outside expression data: a single huge (or tiny) cell next to fractional values
+RANGE_SPIKES = [1e20, -1e20, 1e25, 1e30, 1e40, 1e300, 1e-300, 5e-324]
+
+
+def _range_matrix(N, seed, density):
+    rng = np.random.default_rng(seed)
+    G = len(RANGE_SPIKES) + 1
+    D = np.where(rng.random((G, N)) < density, rng.random((G, N)) * 3, 0.0)
+    for g, v in enumerate(RANGE_SPIKES):
+        D[g, rng.integers(0, N)] = v
+    D[-1, rng.integers(0, N)] = 1e30                      # with 1e-300 and 5e-324 in the same gene
+    D[-1, rng.integers(0, N)] = 1e-300
+    D[-1, rng.integers(0, N)] = 5e-324
+    return D
+
+
+def _check_range(P, LFC, labels, ref):
+    cols = [int(l) for l in labels]
+    rl = ref["lfc"][:, cols]
+    nan = np.isnan(rl)
+    assert np.array_equal(np.isnan(LFC), nan)
+    err = np.abs(LFC[~nan] - rl[~nan])
+    assert err.max(initial=0) <= 1e-10, err.max()
+    _check(P, np.where(nan, 0.0, LFC), labels, {"p": ref["p"], "lfc": np.where(np.isnan(ref["lfc"]), 0.0, ref["lfc"])})
+
+
+def test_log2fc_over_the_whole_double_range_small_n():
+    N, C = 2000, 5
+    D = _range_matrix(N, 37, 0.5)
+    ids = _labels(38, N, C)
+    M = sp.csc_matrix(D)
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    ref = mk.markers_sparse(M, ids, C)
+    pos = [g for g, v in enumerate(RANGE_SPIKES + [1.0]) if v > 0]   # (the -1e20 gene: log2 of a negative ratio, NaN everywhere)
+    lit = mk.markers_literal(D[pos], ids, C)
+    for k in ("p", "lfc"):
+        ref[k][pos] = lit[k]
+    assert np.isnan(ref["lfc"][RANGE_SPIKES.index(-1e20)]).all()
+    _check_range(P, LFC, labels, ref)
+    P2, LFC2, _ = gficf_amd.cluster_markers(M, ids)                  # repeatable, and invariant under a permutation of the cells
+    assert np.array_equal(P, P2) and np.array_equal(LFC, LFC2, equal_nan=True)
+    perm = np.random.default_rng(39).permutation(N)
+    Pp, LFCp, labels_p = gficf_amd.cluster_markers(M[:, perm], ids[perm])
+    order = [list(labels_p).index(l) for l in labels]
+    assert np.array_equal(Pp[:, order], P) and np.array_equal(LFCp[:, order], LFC, equal_nan=True)
+    # the dense two-matrix form once
+    inn = ids == 0
+    out = gficf_amd.rcpp_parallel_WMU_test(D[pos][:, inn], D[pos][:, ~inn])
+    ref = mk.wmu_dense_literal(D[pos][:, inn], D[pos][:, ~inn])
+    assert np.abs(out[:, 1] - ref[:, 1]).max() <= 1e-10
+    assert np.allclose(out[:, 0], ref[:, 0], rtol=1e-12, atol=0)
+
+
+def test_log2fc_over_the_whole_double_range_two_million_cells():
+    """N near 2^21 moves the fixed-point window about ten bits lower.  The reference's sums there: exact ones (fsum) of the
+    cluster's and the rest's values, which its running f64 sums match far inside the 1e-10 bar."""
+    N, C = 2_000_000, 3
+    rng = np.random.default_rng(40)
+    G = len(RANGE_SPIKES) + 1
+    rows, cols, vals = [], [], []
+    for g in range(G):
+        c = np.unique(rng.integers(0, N, 60_000))
+        v = rng.random(len(c)) * 3
+        spikes = [RANGE_SPIKES[g]] if g < len(RANGE_SPIKES) else [1e30, 1e-300, 5e-324]
+        at = rng.choice(np.setdiff1d(np.arange(1000), c), len(spikes), replace=False)
+        rows += [np.full(len(c) + len(at), g)]
+        cols += [c, at]
+        vals += [v, np.array(spikes)]
+    M = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(G, N))
+    ids = _labels(41, N, C)
+    P, LFC, labels = gficf_amd.cluster_markers(M, ids)
+    ref = mk.markers_sparse(M, ids, C)
+    R = M.tocsr()
+    n1 = np.bincount(ids, minlength=C)
+    for g in range(G):
+        row = R[g]
+        cl = ids[row.indices]
+        for c in range(C):
+            s1, s2 = math.fsum(row.data[cl == c]), math.fsum(row.data[cl != c])
+            n2 = N - n1[c]
+            with np.errstate(invalid="ignore"):
+                ref["lfc"][g, c] = np.log2(((s1 + n1[c]) / n1[c]) / ((s2 + n2) / n2))
+    _check_range(P, LFC, labels, ref)
