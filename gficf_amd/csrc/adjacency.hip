@@ -500,7 +500,7 @@ struct gficf_adj_plan {
   double* d_x = nullptr;
 };
 
-void gficf_adj_plan_free(gficf_ctx* ctx) {        // the buffers are pieces of pool slot 6: nothing to release
+void gficf_adj_plan_free(gficf_ctx* ctx) {        // the buffers are pieces of GFICF_SLOT_ADJ_PLAN: nothing to release
   delete ctx->adj_plan;
   ctx->adj_plan = nullptr;
 }
@@ -521,27 +521,27 @@ int gficf_adjacency_host_plan(gficf_ctx* ctx, int64_t N, int64_t n_edges, const 
   const size_t eb = sizeof(double) * (size_t)(n_edges > 0 ? n_edges : 1), cap = (size_t)(n_edges > 0 ? 2 * n_edges : 1);
   const size_t wsb = gficf_adjacency_workspace_bytes(N, n_edges);
   void *d_e = nullptr, *d_ws = nullptr;
-  hipError_t e = gficf_pool_get(ctx, 0, 3 * eb, &d_e);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 1, wsb, &d_ws);
-  gficf_arena ar;
-  const size_t o_ip = ar.take(sizeof(int64_t) * (size_t)(N + 1)), o_ii = ar.take(sizeof(int32_t) * cap), o_xx = ar.take(sizeof(double) * cap);
-  if (e == hipSuccess) e = ar.bind(ctx, 6);
-  p->d_indptr = ar.at<int64_t>(o_ip); p->d_indices = ar.at<int32_t>(o_ii); p->d_x = ar.at<double>(o_xx);
+  gficf_host_io io{ctx, "gficf_adjacency_host_plan"};
+  io.get(GFICF_SLOT_STAGE0, 3 * eb, &d_e);
+  io.get(GFICF_SLOT_STAGE1, wsb, &d_ws);
+  gficf_carver cv;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    p->d_indptr = cv.take<int64_t>((size_t)(N + 1)); p->d_indices = cv.take<int32_t>(cap); p->d_x = cv.take<double>(cap);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_ADJ_PLAN);
+  }
   double* d_from = (double*)d_e;
   double* d_to = d_from + (n_edges > 0 ? n_edges : 1);
   double* d_w = d_to + (n_edges > 0 ? n_edges : 1);
-  if (e == hipSuccess && n_edges > 0) e = hipMemcpyAsync(d_from, from, eb, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && n_edges > 0) e = hipMemcpyAsync(d_to, to, eb, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && n_edges > 0) e = hipMemcpyAsync(d_w, weight, eb, hipMemcpyHostToDevice, ctx->stream);
+  io.up(d_from, from, sizeof(double) * (size_t)n_edges);
+  io.up(d_to, to, sizeof(double) * (size_t)n_edges);
+  io.up(d_w, weight, sizeof(double) * (size_t)n_edges);
   int rc = GFICF_OK;
   int64_t total = 0;
-  if (e == hipSuccess) {
+  if (io.ok()) {
     rc = gficf_adjacency_device(ctx, N, n_edges, nullptr, d_from, d_to, d_w, 0, d_ws, wsb, p->d_indptr, p->d_indices, p->d_x);
-    if (!rc) e = hipMemcpyAsync(&total, p->d_indptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+    if (!rc) io.down(&total, p->d_indptr + N, sizeof(int64_t));
   }
-  if (e != hipSuccess) { gficf_set_error("HIP failure in gficf_adjacency_host_plan: %s", hipGetErrorString(e)); rc = GFICF_ERR_HIP; }
+  rc = io.finish(rc);
   if (rc) { gficf_adj_plan_free(ctx); return rc; }
   p->nnz = total;
   *nnz = total;
@@ -558,17 +558,17 @@ int gficf_adjacency_host_finish(gficf_ctx* ctx, void* indptr, int indptr_is_i64,
     gficf_prefault(indices, sizeof(int32_t) * (size_t)p->nnz);
     gficf_prefault(x, sizeof(double) * (size_t)p->nnz);
   }
-  hipError_t e = hipMemcpyAsync(ip.data(), p->d_indptr, sizeof(int64_t) * ip.size(), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && p->nnz > 0) e = hipMemcpyAsync(indices, p->d_indices, sizeof(int32_t) * (size_t)p->nnz, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && p->nnz > 0) e = hipMemcpyAsync(x, p->d_x, sizeof(double) * (size_t)p->nnz, hipMemcpyDeviceToHost, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) {
+  gficf_host_io io{ctx, "gficf_adjacency_host_finish"};
+  io.down(ip.data(), p->d_indptr, sizeof(int64_t) * ip.size());
+  io.down(indices, p->d_indices, sizeof(int32_t) * (size_t)p->nnz);
+  io.down(x, p->d_x, sizeof(double) * (size_t)p->nnz);
+  const int rc = io.drain(GFICF_OK);
+  if (!rc) {
     if (indptr_is_i64) std::memcpy(indptr, ip.data(), sizeof(int64_t) * ip.size());
     else for (size_t c = 0; c < ip.size(); ++c) ((int32_t*)indptr)[c] = (int32_t)ip[c];
   }
   gficf_adj_plan_free(ctx);
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_adjacency_host_finish: %s", hipGetErrorString(e));
-  return GFICF_OK;
+  return rc;
 }
 
 }  // extern "C"

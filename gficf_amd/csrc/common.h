@@ -22,7 +22,22 @@ constexpr uint32_t GFICF_ST_SET_OVERFLOW = 128u;  // Jaccard, distinct-ids mode,
 constexpr uint32_t GFICF_ST_NOT_GROUPED = 256u;  // adjacency: the edge list was promised grouped by source cell and is not
 constexpr uint32_t GFICF_ST_HALO_OVERFLOW = 32u; // sharded Jaccard, halo form: a block names more rows of one owner than the request slots hold
 
-constexpr int GFICF_POOL_SLOTS = 9;
+// Slots of the context's grow-only device pool (gficf_ctx::pool; kept between calls, released at destroy or by gficf_ctx_trim: no
+// host entry allocates device memory per call).  A slot is one block: whoever takes it owns all of it until its work has drained.
+// The rule behind the assignment: a host entry must not stage into a slot that a device entry it calls draws from.
+enum gficf_pool_slot {
+  GFICF_SLOT_STAGE0,           // staging of the one-call host entries (inputs, outputs, workspace of the device entry they call)
+  GFICF_SLOT_STAGE1,
+  GFICF_SLOT_STAGE2,
+  GFICF_SLOT_DEV_SIG_ORDER,    // drawn by gficf_cluster_signatures_device (cluster ordering scratch); a fourth staging slot of the host
+                               // entries that never reach it: gficf_knn_host, gficf_jaccard_coeff_host
+  GFICF_SLOT_GFICF_PLAN,       // GF-ICF host plan: lives from the plan call to the finish call
+  GFICF_SLOT_EDGE_PLAN,        // filtered-edge plan, likewise
+  GFICF_SLOT_ADJ_PLAN,         // adjacency plan, likewise
+  GFICF_SLOT_GFICF_OUT,        // outputs of the GF-ICF finish call
+  GFICF_SLOT_DEV_COUNT_PARTS,  // drawn by the GF-ICF count pass (device entry): per-workgroup partial histograms
+  GFICF_POOL_SLOTS
+};
 
 struct gficf_host_plan;  // gficf_csc.hip
 struct gficf_edge_plan;  // jaccard.hip
@@ -59,11 +74,7 @@ struct gficf_ctx {
   gficf_host_plan* plan = nullptr;
   gficf_edge_plan* edge_plan = nullptr;
   gficf_adj_plan* adj_plan = nullptr;
-  // grow-only device scratch of the host entry points (kept between calls, released at destroy or by
-  // gficf_ctx_trim): slots 0-3 scratch of one-call entries, 4 GF-ICF host plan, 5 filtered-edge plan,
-  // 6 adjacency plan, 7 outputs of the GF-ICF finish call, 8 per-workgroup partial histograms of the GF-ICF count pass
-  // (the one scratch a device entry draws from the pool).  No host entry allocates device memory per call.
-  void* pool[GFICF_POOL_SLOTS] = {};
+  void* pool[GFICF_POOL_SLOTS] = {};    // grow-only device scratch, one block per gficf_pool_slot
   size_t pool_bytes[GFICF_POOL_SLOTS] = {};
   // grow-only PINNED host staging (the compact return of gficf_jaccard_host: uint16 counts land here before the host expands them)
   void* h_stage = nullptr;
@@ -75,26 +86,15 @@ struct gficf_ctx {
   void (*print_fn)(const char*) = nullptr;
 };
 
-// Device scratch slot of at least `bytes` bytes (reallocated only when it has to grow).
+// Device scratch slot (a gficf_pool_slot) of at least `bytes` bytes, reallocated only when it has to grow.  The slot stays an int in
+// the signature: libgficf_markers.so links this symbol, and one built before the slots had names must keep loading.
 hipError_t gficf_pool_get(gficf_ctx* ctx, int slot, size_t bytes, void** out);
 // Pinned host staging of at least `bytes` bytes (same policy; released by gficf_ctx_trim / destroy).
 hipError_t gficf_host_stage_get(gficf_ctx* ctx, size_t bytes, void** out);
 
-// Sub-allocation of one pool slot: take() the pieces (256 B aligned), then bind() once.
-struct gficf_arena {
-  size_t off = 0;
-  char* base = nullptr;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off = (off + (bytes ? bytes : 1) + 255) & ~(size_t)255;
-    return o;
-  }
-  hipError_t bind(gficf_ctx* ctx, int slot) { return gficf_pool_get(ctx, slot, off ? off : 256, (void**)&base); }
-  template <typename T>
-  T* at(size_t o) const { return reinterpret_cast<T*>(base + o); }
-};
-
-// Carving of a caller's workspace: take() the pieces in order (each 256 B aligned); base == nullptr only counts, total() is the size to ask for.
+// Carving of one block: take() the pieces in order (each 256 B aligned).  base == nullptr only counts.
+//   a caller's workspace: total() is the size to ask for, then carve again with base set;
+//   a pool slot:  for (int pass = 0; pass < 2; ++pass) { p = cv.take<T>(n); ...; if (pass == 0) e = cv.bind(ctx, slot); }
 struct gficf_carver {
   char* base = nullptr;
   size_t off = 0;
@@ -105,6 +105,13 @@ struct gficf_carver {
     return p;
   }
   size_t total() const { return off + 256; }
+  // after the counting pass: the slot grown to the pieces counted (at least 256 B, so an empty problem still gets non-null
+  // pointers), and the carver rewound for the carving pass.  On failure base stays NULL.
+  hipError_t bind(gficf_ctx* ctx, gficf_pool_slot slot) {
+    const size_t bytes = off ? off : 256;
+    off = 0;
+    return gficf_pool_get(ctx, slot, bytes, (void**)&base);
+  }
 };
 
 // banner lines of the host entries (the reference prints with Rprintf)
@@ -172,6 +179,51 @@ void gficf_set_error(const char* fmt, ...);
     GFICF_HIP_CHECK(hipSetDevice((ctx)->device));                    \
   } while (0)
 
+// ---------------------------------------------------------------- the shape of a host entry
+// check the arguments, carve one pool slot, up() the inputs, call the device entry, down() the results, finish().
+// The rule finish() keeps: never return with a copy from or into the caller's memory in flight; a HIP error wins over anything
+// else; a status code of the device entry is returned as it is.
+
+// entry i of a caller's int32 or int64 column pointer
+inline int64_t gficf_colptr_at(const void* ptr, int ptr_is_i64, int64_t i) {
+  return ptr_is_i64 ? ((const int64_t*)ptr)[i] : (int64_t)((const int32_t*)ptr)[i];
+}
+// The n + 1 entries of such a pointer widened into `out`, their last one in *nnz.  GFICF_ERR_BAD_CSC (naming `what` and the
+// first offending position) unless they start at 0 and never decrease.  (Inline: libgficf_markers.so uses it too, and asks of
+// libgficf_hip.so only what every build of ABI 7 exports.)
+inline int gficf_host_colptr(const void* ptr, int ptr_is_i64, int64_t n, const char* what, std::vector<int64_t>& out, int64_t* nnz) {
+  out.resize((size_t)n + 1);
+  for (int64_t c = 0; c <= n; ++c) out[(size_t)c] = gficf_colptr_at(ptr, ptr_is_i64, c);
+  if (out[0] != 0) GFICF_FAIL(GFICF_ERR_BAD_CSC, "%s[0] = %lld, expected 0", what, (long long)out[0]);
+  for (int64_t c = 0; c < n; ++c)
+    if (out[(size_t)c + 1] < out[(size_t)c]) GFICF_FAIL(GFICF_ERR_BAD_CSC, "%s decreases at position %lld", what, (long long)(c + 1));
+  *nnz = out[(size_t)n];
+  return GFICF_OK;
+}
+
+struct gficf_host_io {
+  gficf_ctx* ctx;
+  const char* entry;            // named in the message of a HIP failure
+  hipError_t e = hipSuccess;    // the first HIP error seen: every later step is skipped
+  bool ok() const { return e == hipSuccess; }
+  void get(gficf_pool_slot slot, size_t bytes, void** out) {
+    if (ok()) e = gficf_pool_get(ctx, slot, bytes, out);
+  }
+  void up(void* dst, const void* src, size_t bytes) {
+    if (ok() && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+  }
+  void down(void* dst, const void* src, size_t bytes) {
+    if (ok() && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  // waits for the stream without reading the status word; the HIP error if one was seen, else rc
+  int drain(int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (!ok()) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in %s: %s", entry, hipGetErrorString(e));
+    return rc;
+  }
+  int finish(int rc) { return (!ok() || rc) ? drain(rc) : gficf_ctx_sync(ctx); }
+};
+
 __host__ __device__ static inline int64_t gficf_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // smallest b in 1..32 with 2^b > n: a value in [0, n] (an id in [0, n) and the marker n) fits b bits
@@ -237,7 +289,7 @@ __device__ inline int64_t gficf_lookback_exclusive(unsigned long long* ws, int64
 // Next epoch of the context's look-back workspace (zeroes the workspace on wrap); checks that n_tiles descriptors fit.
 int gficf_ws_next_epoch(gficf_ctx* ctx, int64_t n_tiles, uint32_t* epoch);
 
-// In-place exclusive scan of n int64 values on the context's stream (scan.hip).
+// In-place exclusive scan of n int64 values on the context's stream (ctx.hip).
 // One launch (decoupled look-back); uses ctx->d_ws.  Sums must stay in [0, 2^40): a tile total or a running prefix outside that
 // raises GFICF_ST_BAD_CSC (GFICF_ERR_BAD_CSC at the next gficf_ctx_sync).  n beyond 131,071 tiles: GFICF_ERR_UNSUPPORTED.
 int gficf_exclusive_scan_i64(gficf_ctx* ctx, int64_t* d_data, int64_t n);

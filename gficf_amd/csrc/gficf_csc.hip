@@ -71,7 +71,7 @@ static int launch_count(gficf_ctx* ctx, int64_t G, const int32_t* d_rowidx, cons
       GFICF_HIP_CHECK(hipFuncSetAttribute((const void*)k_gene_count<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
       attr_set[ctx->device & 63] = true;
     }
-    GFICF_HIP_CHECK(gficf_pool_get(ctx, 8, sizeof(uint32_t) * (size_t)Gp * (size_t)blocks, (void**)&d_part));
+    GFICF_HIP_CHECK(gficf_pool_get(ctx, GFICF_SLOT_DEV_COUNT_PARTS, sizeof(uint32_t) * (size_t)Gp * (size_t)blocks, (void**)&d_part));
   } else if (blocks > (int64_t)ctx->num_cus * 2) {
     blocks = (int64_t)ctx->num_cus * 2;
   }
@@ -243,7 +243,7 @@ static int signatures_launch(gficf_ctx* ctx, int64_t G, int64_t n_cells, const i
     // everything else the context enqueues)
     const size_t off_cur = ((size_t)(C + 1) * 8 + 255) & ~(size_t)255, off_ord = (off_cur + (size_t)C * 4 + 255) & ~(size_t)255;
     void* scratch = nullptr;
-    GFICF_HIP_CHECK(gficf_pool_get(ctx, 3, off_ord + (size_t)n_cells * 4, &scratch));
+    GFICF_HIP_CHECK(gficf_pool_get(ctx, GFICF_SLOT_DEV_SIG_ORDER, off_ord + (size_t)n_cells * 4, &scratch));
     int64_t* const start = (int64_t*)scratch;
     uint32_t* const cursor = (uint32_t*)((char*)scratch + off_cur);
     int32_t* const order = (int32_t*)((char*)scratch + off_ord);
@@ -282,33 +282,29 @@ int gficf_cluster_signatures_host(gficf_ctx* ctx, int64_t G, int64_t N, const vo
   if (G < 0 || N < 0 || C < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "negative size");
   if (G == 0 || C == 0) return GFICF_OK;
   if (!colptr || !out || (N > 0 && !cluster)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
-  std::vector<int64_t> cp((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c)
-    cp[(size_t)c] = colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c];
-  for (int64_t c = 0; c < N; ++c)
-    if (cp[(size_t)c + 1] < cp[(size_t)c] || cp[0] != 0) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr not monotone at cell %lld", (long long)c);
-  const int64_t nnz = cp[(size_t)N];
+  std::vector<int64_t> cp;
+  int64_t nnz = 0;
+  int rc = gficf_host_colptr(colptr, colptr_is_i64, N, "colptr", cp, &nnz);
+  if (rc) return rc;
   if (nnz > 0 && (!rowidx || !x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const size_t nsz = (size_t)(nnz > 0 ? nnz : 1), csz = (size_t)(N > 0 ? N : 1);
-  gficf_arena ar;                                   // pool slot 0 (the device form takes slot 3 for its own scratch)
-  const size_t o_cp = ar.take(sizeof(int64_t) * ((size_t)N + 1)), o_ri = ar.take(sizeof(int32_t) * nsz), o_x = ar.take(sizeof(double) * nsz);
-  const size_t o_cl = ar.take(sizeof(int32_t) * csz), o_out = ar.take(sizeof(double) * (size_t)G * (size_t)C);
-  hipError_t e = ar.bind(ctx, 0);
-  int64_t* const d_cp = ar.at<int64_t>(o_cp); int32_t* const d_ri = ar.at<int32_t>(o_ri); double* const d_x = ar.at<double>(o_x);
-  int32_t* const d_cl = ar.at<int32_t>(o_cl); double* const d_out = ar.at<double>(o_out);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cp, cp.data(), sizeof(int64_t) * cp.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_ri, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && N > 0) e = hipMemcpyAsync(d_cl, cluster, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, ctx->stream);
-  int rc = GFICF_OK;
-  if (e == hipSuccess) {
-    rc = gficf_cluster_signatures_device(ctx, G, N, d_cp, d_ri, d_x, d_cl, C, d_out);
-    if (!rc) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)G * (size_t)C, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+  gficf_host_io io{ctx, "gficf_cluster_signatures_host"};
+  gficf_carver cv;
+  int64_t* d_cp; int32_t *d_ri, *d_cl; double *d_x, *d_out;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_cp = cv.take<int64_t>((size_t)N + 1); d_ri = cv.take<int32_t>(nsz); d_x = cv.take<double>(nsz);
+    d_cl = cv.take<int32_t>(csz); d_out = cv.take<double>((size_t)G * (size_t)C);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);      // (the device form draws GFICF_SLOT_DEV_SIG_ORDER)
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_cluster_signatures_host: %s", hipGetErrorString(e));
-  return rc;
+  io.up(d_cp, cp.data(), sizeof(int64_t) * cp.size());
+  io.up(d_ri, rowidx, sizeof(int32_t) * (size_t)nnz);
+  io.up(d_x, x, sizeof(double) * (size_t)nnz);
+  io.up(d_cl, cluster, sizeof(int32_t) * (size_t)N);
+  if (io.ok()) {
+    rc = gficf_cluster_signatures_device(ctx, G, N, d_cp, d_ri, d_x, d_cl, C, d_out);
+    if (!rc) io.down(out, d_out, sizeof(double) * (size_t)G * (size_t)C);
+  }
+  return io.finish(rc);
 }
 
 size_t gficf_csc_genes_bytes(int64_t G) {
@@ -394,7 +390,7 @@ int gficf_csc_exact_device(gficf_ctx* ctx, int64_t G, int64_t N, const int64_t* 
 }  // extern "C"
 
 // ------------------------------------------------------------------- host form (R glue)
-// Device buffers are pieces of the context's pool (slot 4 for the plan, slot 7 for the outputs of the finish
+// Device buffers are pieces of the context's pool (GFICF_SLOT_GFICF_PLAN for the plan, GFICF_SLOT_GFICF_OUT for the outputs of the finish
 // call): kept between calls, nothing is allocated or freed per call.
 struct gficf_host_plan {
   int64_t G = 0, N = 0, nnz = 0, nnz_kept = 0, g_kept = 0;
@@ -425,7 +421,7 @@ void gficf_host_plan_free(gficf_ctx* ctx) {
 struct ColPtr {
   const void* p;
   int is64;
-  int64_t operator[](int64_t c) const { return is64 ? ((const int64_t*)p)[c] : (int64_t)((const int32_t*)p)[c]; }
+  int64_t operator[](int64_t c) const { return gficf_colptr_at(p, is64, c); }
 };
 
 // returns GFICF_OK or GFICF_ERR_BAD_CSC (some cell's kept entries do not fill [kept_colptr[c], kept_colptr[c+1]) exactly); sets no message:
@@ -494,17 +490,6 @@ static int kept_values(int64_t G, int64_t N, ColPtr cp, const int32_t* rowidx, c
   return bad.load() ? GFICF_ERR_BAD_CSC : GFICF_OK;
 }
 
-#define PLAN_HIP(expr)                                                                              \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) {                                                                         \
-      gficf_set_error("%s failed: %s", #expr, hipGetErrorString(_e));                               \
-      (void)hipStreamSynchronize(ctx->stream);                                                      \
-      gficf_host_plan_free(ctx);                                                                    \
-      return GFICF_ERR_HIP;                                                                         \
-    }                                                                                               \
-  } while (0)
-
 extern "C" {
 
 int gficf_normalize_csc_host_plan(gficf_ctx* ctx, int64_t G, int64_t N, const void* colptr, int colptr_is_i64,
@@ -514,48 +499,42 @@ int gficf_normalize_csc_host_plan(gficf_ctx* ctx, int64_t G, int64_t N, const vo
   if (G < 0 || N < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "negative dimension");
   if (!colptr || !G_kept || !nnz_kept) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   gficf_host_plan_free(ctx);
-  std::vector<int64_t> cp((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c)
-    cp[(size_t)c] = colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c];
-  if (cp[0] != 0) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr[0] = %lld, expected 0", (long long)cp[0]);
-  for (int64_t c = 0; c < N; ++c)
-    if (cp[(size_t)c + 1] < cp[(size_t)c]) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr not monotone at cell %lld", (long long)c);
-  const int64_t nnz = cp[(size_t)N];
+  std::vector<int64_t> cp;
+  int64_t nnz = 0;
+  int rc = gficf_host_colptr(colptr, colptr_is_i64, N, "colptr", cp, &nnz);
+  if (rc) return rc;
   if (nnz > 0 && (!rowidx || !x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   gficf_host_plan* p = new gficf_host_plan();
   ctx->plan = p;
   p->G = G; p->N = N; p->nnz = nnz; p->colptr_is_i64 = colptr_is_i64;
   const size_t gsz = (size_t)(G > 0 ? G : 1), nsz = (size_t)(nnz > 0 ? nnz : 1);
-  gficf_arena ar;
-  const size_t o_cp = ar.take(sizeof(int64_t) * ((size_t)N + 1)), o_ri = ar.take(sizeof(int32_t) * nsz), o_x = ar.take(sizeof(double) * nsz);
-  const size_t o_nt = ar.take(sizeof(int64_t) * gsz), o_keep = ar.take(gsz), o_genes = ar.take(gficf_csc_genes_bytes(G));
-  const size_t o_w = ar.take(sizeof(double) * gsz), o_gk = ar.take(sizeof(int64_t)), o_ocp = ar.take(sizeof(int64_t) * ((size_t)N + 1));
-  const size_t o_win = ar.take(sizeof(double) * gsz);
-  PLAN_HIP(ar.bind(ctx, 4));
-  p->d_colptr = ar.at<int64_t>(o_cp); p->d_rowidx = ar.at<int32_t>(o_ri); p->d_x = ar.at<double>(o_x);
-  p->d_nt = ar.at<int64_t>(o_nt); p->d_keep = ar.at<uint8_t>(o_keep); p->d_genes = ar.at<gficf_gene_entry>(o_genes);
-  p->d_w = ar.at<double>(o_w); p->d_gkept = ar.at<int64_t>(o_gk); p->d_out_colptr = ar.at<int64_t>(o_ocp);
-  PLAN_HIP(hipMemcpyAsync(p->d_colptr, cp.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, ctx->stream));
-  if (nnz > 0) {
-    PLAN_HIP(hipMemcpyAsync(p->d_rowidx, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    PLAN_HIP(hipMemcpyAsync(p->d_x, x, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+  gficf_host_io io{ctx, "gficf_normalize_csc_host_plan"};
+  gficf_carver cv;
+  double* d_w_in;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    p->d_colptr = cv.take<int64_t>((size_t)N + 1); p->d_rowidx = cv.take<int32_t>(nsz); p->d_x = cv.take<double>(nsz);
+    p->d_nt = cv.take<int64_t>(gsz); p->d_keep = cv.take<uint8_t>(gsz); p->d_genes = (gficf_gene_entry*)cv.take<char>(gficf_csc_genes_bytes(G));
+    p->d_w = cv.take<double>(gsz); p->d_gkept = cv.take<int64_t>(1); p->d_out_colptr = cv.take<int64_t>((size_t)N + 1);
+    d_w_in = cv.take<double>(gsz);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_GFICF_PLAN);
   }
-  if (w_in && G > 0) {
-    p->d_w_in = ar.at<double>(o_win);
-    PLAN_HIP(hipMemcpyAsync(p->d_w_in, w_in, sizeof(double) * (size_t)G, hipMemcpyHostToDevice, ctx->stream));
-  }
-  PLAN_HIP(hipMemsetAsync(p->d_nt, 0, sizeof(int64_t) * gsz, ctx->stream));
-  int rc = gficf_csc_count_device(ctx, G, N, p->d_colptr, p->d_rowidx, p->d_x, nnz, p->d_nt);
-  if (!rc) rc = gficf_csc_genes_device(ctx, G, N, p->d_nt, prop_min, prop_max, p->d_w_in, p->d_keep, p->d_genes, p->d_w, p->d_gkept);
-  if (!rc) rc = gficf_csc_colptr_device(ctx, G, N, p->d_colptr, p->d_rowidx, p->d_keep, p->d_gkept, p->d_out_colptr);
+  if (w_in && G > 0) p->d_w_in = d_w_in;
+  io.up(p->d_colptr, cp.data(), sizeof(int64_t) * ((size_t)N + 1));
+  io.up(p->d_rowidx, rowidx, sizeof(int32_t) * (size_t)nnz);
+  io.up(p->d_x, x, sizeof(double) * (size_t)nnz);
+  if (p->d_w_in) io.up(p->d_w_in, w_in, sizeof(double) * (size_t)G);
+  if (io.ok()) io.e = hipMemsetAsync(p->d_nt, 0, sizeof(int64_t) * gsz, ctx->stream);
   int64_t hk[2] = {0, 0};
-  if (!rc) {
-    PLAN_HIP(hipMemcpyAsync(&hk[0], p->d_gkept, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PLAN_HIP(hipMemcpyAsync(&hk[1], p->d_out_colptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    rc = gficf_ctx_sync(ctx);
-  } else {
-    (void)hipStreamSynchronize(ctx->stream);
+  if (io.ok()) {
+    rc = gficf_csc_count_device(ctx, G, N, p->d_colptr, p->d_rowidx, p->d_x, nnz, p->d_nt);
+    if (!rc) rc = gficf_csc_genes_device(ctx, G, N, p->d_nt, prop_min, prop_max, p->d_w_in, p->d_keep, p->d_genes, p->d_w, p->d_gkept);
+    if (!rc) rc = gficf_csc_colptr_device(ctx, G, N, p->d_colptr, p->d_rowidx, p->d_keep, p->d_gkept, p->d_out_colptr);
+    if (!rc) {
+      io.down(&hk[0], p->d_gkept, sizeof(int64_t));
+      io.down(&hk[1], p->d_out_colptr + N, sizeof(int64_t));
+    }
   }
+  rc = io.finish(rc);
   if (rc) { gficf_host_plan_free(ctx); return rc; }
   p->g_kept = hk[0];
   p->nnz_kept = hk[1];
@@ -574,11 +553,13 @@ static int host_finish(gficf_ctx* ctx, uint8_t* keep, int64_t* nt, double* w, vo
   const bool want_raw = out_raw_x != nullptr && p->nnz_kept > 0;
   if (want_raw && (!raw_rowidx || !raw_x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "the raw values of the kept rows need the matrix's rowidx and x again");
   const size_t ksz = (size_t)(p->nnz_kept > 0 ? p->nnz_kept : 1);
-  gficf_arena ar;
-  const size_t o_ri = ar.take(sizeof(int32_t) * ksz), o_x = ar.take(sizeof(double) * ksz);
-  PLAN_HIP(ar.bind(ctx, 7));
-  int32_t* const d_ori = ar.at<int32_t>(o_ri);
-  double* const d_ox = ar.at<double>(o_x);
+  gficf_host_io io{ctx, "gficf_normalize_csc_host_finish"};
+  gficf_carver cv;
+  int32_t* d_ori; double* d_ox;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_ori = cv.take<int32_t>(ksz); d_ox = cv.take<double>(ksz);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_GFICF_OUT);
+  }
   std::vector<int64_t> cp((size_t)p->N + 1), cp_in;
   std::vector<uint8_t> keep_h;
   std::thread raw_thread;
@@ -588,12 +569,13 @@ static int host_finish(gficf_ctx* ctx, uint8_t* keep, int64_t* nt, double* w, vo
     // kept rows are then gathered by host threads from the caller's own vectors WHILE the scaling pass runs and its results come back
     cp_in.resize((size_t)p->N + 1);
     keep_h.resize((size_t)(p->G > 0 ? p->G : 1));
-    PLAN_HIP(hipMemcpyAsync(cp.data(), p->d_out_colptr, sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost, ctx->stream));
-    PLAN_HIP(hipMemcpyAsync(cp_in.data(), p->d_colptr, sizeof(int64_t) * cp_in.size(), hipMemcpyDeviceToHost, ctx->stream));
-    if (p->G > 0) PLAN_HIP(hipMemcpyAsync(keep_h.data(), p->d_keep, (size_t)p->G, hipMemcpyDeviceToHost, ctx->stream));
-    PLAN_HIP(hipStreamSynchronize(ctx->stream));
+    io.down(cp.data(), p->d_out_colptr, sizeof(int64_t) * cp.size());
+    io.down(cp_in.data(), p->d_colptr, sizeof(int64_t) * cp_in.size());
+    io.down(keep_h.data(), p->d_keep, (size_t)p->G);
   }
-  int rc = gficf_csc_scale_device(ctx, p->G, p->N, p->d_colptr, p->d_rowidx, p->d_x, p->nnz, p->d_genes, p->d_gkept,
+  int rc = (want_raw || !io.ok()) ? io.drain(GFICF_OK) : GFICF_OK;
+  if (rc) { gficf_host_plan_free(ctx); return rc; }
+  rc = gficf_csc_scale_device(ctx, p->G, p->N, p->d_colptr, p->d_rowidx, p->d_x, p->nnz, p->d_genes, p->d_gkept,
                                   p->d_out_colptr, d_ori, d_ox);
   if (!rc && want_raw) {
     const int64_t G = p->G, N = p->N;
@@ -613,21 +595,18 @@ static int host_finish(gficf_ctx* ctx, uint8_t* keep, int64_t* nt, double* w, vo
     const size_t xb = sizeof(double) * (size_t)p->nnz_kept;
     try { fault_x = std::thread([ox, xb] { gficf_prefault(ox, xb); }); } catch (...) { }
   }
-  hipError_t e = hipSuccess;
   if (!rc) {
-    if (!want_raw) e = hipMemcpyAsync(cp.data(), p->d_out_colptr, sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && p->nnz_kept > 0) e = hipMemcpyAsync(out_rowidx, d_ori, sizeof(int32_t) * (size_t)p->nnz_kept, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && keep && p->G > 0) e = hipMemcpyAsync(keep, p->d_keep, (size_t)p->G, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && nt && p->G > 0) e = hipMemcpyAsync(nt, p->d_nt, sizeof(int64_t) * (size_t)p->G, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && w && p->G > 0) e = hipMemcpyAsync(w, p->d_w, sizeof(double) * (size_t)p->G, hipMemcpyDeviceToHost, ctx->stream);
+    if (!want_raw) io.down(cp.data(), p->d_out_colptr, sizeof(int64_t) * cp.size());
+    io.down(out_rowidx, d_ori, sizeof(int32_t) * (size_t)p->nnz_kept);
+    if (keep) io.down(keep, p->d_keep, (size_t)p->G);
+    if (nt) io.down(nt, p->d_nt, sizeof(int64_t) * (size_t)p->G);
+    if (w) io.down(w, p->d_w, sizeof(double) * (size_t)p->G);
     if (fault_x.joinable()) fault_x.join();
-    if (e == hipSuccess && p->nnz_kept > 0) e = hipMemcpyAsync(out_x, d_ox, sizeof(double) * (size_t)p->nnz_kept, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) rc = gficf_ctx_sync(ctx);
+    io.down(out_x, d_ox, sizeof(double) * (size_t)p->nnz_kept);
   }
+  rc = io.finish(rc);
   if (fault_x.joinable()) fault_x.join();
   if (raw_thread.joinable()) raw_thread.join();
-  if (e != hipSuccess || rc) (void)hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) { gficf_set_error("HIP failure in gficf_normalize_csc_host_finish: %s", hipGetErrorString(e)); rc = GFICF_ERR_HIP; }
   if (!rc && raw_rc) {
     gficf_set_error("the rowidx / x handed to the finish call are not the matrix of the plan (the kept entries of some cell do not match its count)");
     rc = raw_rc;

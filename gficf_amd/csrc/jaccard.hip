@@ -712,21 +712,19 @@ static int gficf_jaccard_host_body(gficf_ctx* ctx, const void* idx, int idx_is_f
       GFICF_FAIL(GFICF_ERR_UNSUPPORTED, "non-integer ids (GFICF_HIP_TRUNCATE_IDS) with k = %d: the truncating kernel covers k <= %d", k, GFICF_JACCARD_MAX_K);
     void* d_idx = nullptr;
     double* d_rmat = nullptr;
-    hipError_t e = gficf_pool_get(ctx, 0, sizeof(double) * (size_t)ld * (size_t)k, &d_idx);
-    if (e == hipSuccess) e = gficf_pool_get(ctx, 2, sizeof(double) * 3 * (size_t)E, (void**)&d_rmat);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_idx, idx, sizeof(double) * (size_t)ld * (size_t)k, hipMemcpyHostToDevice, ctx->stream);
-    rc = GFICF_OK;
-    if (e == hipSuccess) {
+    gficf_host_io io{ctx, "gficf_jaccard_host"};
+    io.get(GFICF_SLOT_STAGE0, sizeof(double) * (size_t)ld * (size_t)k, &d_idx);
+    io.get(GFICF_SLOT_STAGE2, sizeof(double) * 3 * (size_t)E, (void**)&d_rmat);
+    io.up(d_idx, idx, sizeof(double) * (size_t)ld * (size_t)k);
+    if (io.ok()) {
       int64_t blocks = gficf_ceil_div(N, 4);
       if (blocks > (int64_t)ctx->num_cus * 8) blocks = (int64_t)ctx->num_cus * 8;
       hipLaunchKernelGGL(k_jaccard_trunc_f64, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const double*)d_idx, N, k, ld, d_rmat, d_rmat + E,
                          d_rmat + 2 * E, ctx->d_status);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(rmat, d_rmat, sizeof(double) * 3 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) rc = gficf_ctx_sync(ctx);
-      else (void)hipStreamSynchronize(ctx->stream);
+      io.e = hipGetLastError();
+      io.down(rmat, d_rmat, sizeof(double) * 3 * (size_t)E);
     }
-    if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_jaccard_host: %s", hipGetErrorString(e));
+    rc = io.finish(GFICF_OK);
     if (rc) return rc;
   } else if (E > 0 && idx && rmat && ld >= N && E >= host_compact_min_edges()) {
     // ---- the compact return (round 5): the 24 B row of an edge is a function of (i, idx[i,j], u), and idx is on the host already.
@@ -757,20 +755,18 @@ static int gficf_jaccard_host_body(gficf_ctx* ctx, const void* idx, int idx_is_f
     int32_t* d_table = nullptr;
     double* d_rmat = nullptr;
     // device scratch comes from the context's grow-only pool: no hipMalloc/hipFree per call
-    hipError_t e = gficf_pool_get(ctx, 0, esz * (size_t)ld * (size_t)k, &d_idx);
-    if (e == hipSuccess) e = gficf_pool_get(ctx, 1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table);
-    if (e == hipSuccess) e = gficf_pool_get(ctx, 2, sizeof(double) * 3 * (size_t)E, (void**)&d_rmat);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_idx, idx, esz * (size_t)ld * (size_t)k, hipMemcpyHostToDevice, ctx->stream);
-    rc = GFICF_OK;
-    if (e == hipSuccess) {
+    gficf_host_io io{ctx, "gficf_jaccard_host"};
+    io.get(GFICF_SLOT_STAGE0, esz * (size_t)ld * (size_t)k, &d_idx);
+    io.get(GFICF_SLOT_STAGE1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table);
+    io.get(GFICF_SLOT_STAGE2, sizeof(double) * 3 * (size_t)E, (void**)&d_rmat);
+    io.up(d_idx, idx, esz * (size_t)ld * (size_t)k);
+    if (io.ok()) {
       rc = gficf_jaccard_device(ctx, d_idx, idx_is_f64, N, k, ld, d_table, d_rmat, nullptr);
       gficf_advise_hugepages(rmat, sizeof(double) * 3 * (size_t)E);  // (a fresh R matrix of 4 MB or more: huge pages for its first touch by the copy;
       gficf_prefault(rmat, sizeof(double) * 3 * (size_t)E);          //  >= 16 MB: also touched from several threads while the kernels run)
-      if (rc == GFICF_OK) e = hipMemcpyAsync(rmat, d_rmat, sizeof(double) * 3 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream);
-      if (rc == GFICF_OK && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-      else (void)hipStreamSynchronize(ctx->stream);
+      if (!rc) io.down(rmat, d_rmat, sizeof(double) * 3 * (size_t)E);
     }
-    if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_jaccard_host: %s", hipGetErrorString(e));
+    rc = io.finish(rc);
     if (rc) return rc;
   }
   if (print_output) gficf_print(ctx, "Done!!\n");  // reference :77
@@ -792,23 +788,21 @@ static int gficf_jaccard_counts_host_body(gficf_ctx* ctx, const void* idx, int i
   void* d_idx = nullptr;
   int32_t* d_table = nullptr;
   uint16_t* d_u = nullptr;
-  hipError_t e = gficf_pool_get(ctx, 0, esz * (size_t)ld * (size_t)k, &d_idx);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 2, sizeof(uint16_t) * (size_t)E, (void**)&d_u);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_idx, idx, esz * (size_t)ld * (size_t)k, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
+  gficf_host_io io{ctx, "gficf_jaccard_counts_host"};
+  io.get(GFICF_SLOT_STAGE0, esz * (size_t)ld * (size_t)k, &d_idx);
+  io.get(GFICF_SLOT_STAGE1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table);
+  io.get(GFICF_SLOT_STAGE2, sizeof(uint16_t) * (size_t)E, (void**)&d_u);
+  io.up(d_idx, idx, esz * (size_t)ld * (size_t)k);
+  if (io.ok()) {
     EdgeOut o{nullptr, nullptr, nullptr, nullptr, d_u, 0};
     if (direct_applies(ctx, N, k)) rc = launch_direct(ctx, d_idx, idx_is_f64, N, k, ld, o);      // small problem: one launch, no table
     else {
       rc = gficf_jaccard_ingest_device(ctx, d_idx, idx_is_f64, N, k, ld, N, d_table);
       if (!rc) rc = launch_edges_k(ctx, (const uint32_t*)d_table, N, k, 0, N, o);
     }
-    if (!rc) e = hipMemcpyAsync(u, d_u, sizeof(uint16_t) * (size_t)E, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+    if (!rc) io.down(u, d_u, sizeof(uint16_t) * (size_t)E);
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_jaccard_counts_host: %s", hipGetErrorString(e));
-  return rc;
+  return io.finish(rc);
 }
 
 /* Host-side expansion of the counts into the reference's (N*k) x 3 matrix (src/rcpp_parallel_jaccard_coeff.cpp:48-52):
@@ -975,7 +969,7 @@ int gficf_jaccard_edges_filtered_mapped(gficf_ctx* ctx, const int32_t* d_table, 
 extern "C" {
 
 // host form of the filtered build: plan runs everything and returns the edge count, finish copies out.
-// Device buffers are pieces of the context's pool slot 5 (kept between calls; nothing is allocated per call).
+// Device buffers are pieces of the context's GFICF_SLOT_EDGE_PLAN (kept between calls; nothing is allocated per call).
 struct gficf_edge_plan {
   int64_t n_edges = 0;
   double* d_from = nullptr;
@@ -1057,27 +1051,23 @@ static int gficf_jaccard_filtered_host_plan_body(gficf_ctx* ctx, const void* idx
   }
   const size_t esz = idx_is_f64 ? sizeof(double) : sizeof(int32_t);
   const int roww = table_fmt(N, k).row_words;
-  gficf_arena ar;
-  const size_t o_idx = ar.take(esz * (size_t)ld * (size_t)k), o_tab = ar.take(sizeof(int32_t) * (size_t)N * (size_t)roww);
-  const size_t o_u = ar.take(sizeof(uint16_t) * (size_t)E), o_ptr = ar.take(sizeof(int64_t) * (size_t)(N + 1));
-  const size_t o_f = ar.take(sizeof(double) * (size_t)E), o_t = ar.take(sizeof(double) * (size_t)E), o_w = ar.take(sizeof(double) * (size_t)E);
-  hipError_t e = ar.bind(ctx, 5);
-  void* d_idx = ar.at<void>(o_idx);
-  int32_t* d_table = ar.at<int32_t>(o_tab);
-  uint16_t* d_u = ar.at<uint16_t>(o_u);
-  int64_t* d_ptr = ar.at<int64_t>(o_ptr);
-  p->d_from = ar.at<double>(o_f); p->d_to = ar.at<double>(o_t); p->d_weight = ar.at<double>(o_w);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_idx, idx, esz * (size_t)ld * (size_t)k, hipMemcpyHostToDevice, ctx->stream);
-  rc = GFICF_OK;
+  gficf_host_io io{ctx, "gficf_jaccard_filtered_host_plan"};
+  gficf_carver cv;
+  void* d_idx; int32_t* d_table; uint16_t* d_u; int64_t* d_ptr;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_idx = cv.take<char>(esz * (size_t)ld * (size_t)k); d_table = cv.take<int32_t>((size_t)N * (size_t)roww);
+    d_u = cv.take<uint16_t>((size_t)E); d_ptr = cv.take<int64_t>((size_t)(N + 1));
+    p->d_from = cv.take<double>((size_t)E); p->d_to = cv.take<double>((size_t)E); p->d_weight = cv.take<double>((size_t)E);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_EDGE_PLAN);
+  }
+  io.up(d_idx, idx, esz * (size_t)ld * (size_t)k);
   int64_t total = 0;
-  if (e == hipSuccess) {
+  if (io.ok()) {
     rc = gficf_jaccard_ingest_device(ctx, d_idx, idx_is_f64, N, k, ld, N, d_table);
     if (!rc) rc = gficf_jaccard_edges_filtered_device(ctx, d_table, N, k, 0, N, d_u, d_ptr, p->d_from, p->d_to, p->d_weight);
-    if (!rc) e = hipMemcpyAsync(&total, d_ptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+    if (!rc) io.down(&total, d_ptr + N, sizeof(int64_t));
   }
-  if (e != hipSuccess) { gficf_set_error("HIP failure in gficf_jaccard_filtered_host_plan: %s", hipGetErrorString(e)); rc = GFICF_ERR_HIP; }
+  rc = io.finish(rc);
   if (rc) { edge_plan_free(ctx); return rc; }
   p->n_edges = total;
   *n_edges = total;
@@ -1101,38 +1091,36 @@ static int gficf_jaccard_coeff_host_body(gficf_ctx* ctx, const void* idx, int id
   const size_t esz = idx_is_f64 ? sizeof(double) : sizeof(int32_t);
   const int roww = table_fmt(N, k).row_words;
   void *d_idx = nullptr, *d_table = nullptr, *d_out = nullptr, *d_aux = nullptr;
-  hipError_t e = gficf_pool_get(ctx, 0, esz * (size_t)ld * (size_t)k, &d_idx);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 1, sizeof(int32_t) * (size_t)N * (size_t)roww, &d_table);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 2, sizeof(double) * 3 * (size_t)E, &d_out);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 3, sizeof(uint16_t) * (size_t)E + 64 + sizeof(int64_t) * (size_t)(N + 1), &d_aux);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_idx, idx, esz * (size_t)ld * (size_t)k, hipMemcpyHostToDevice, ctx->stream);
+  gficf_host_io io{ctx, "gficf_jaccard_coeff_host"};
+  io.get(GFICF_SLOT_STAGE0, esz * (size_t)ld * (size_t)k, &d_idx);
+  io.get(GFICF_SLOT_STAGE1, sizeof(int32_t) * (size_t)N * (size_t)roww, &d_table);
+  io.get(GFICF_SLOT_STAGE2, sizeof(double) * 3 * (size_t)E, &d_out);
+  io.get(GFICF_SLOT_DEV_SIG_ORDER, sizeof(uint16_t) * (size_t)E + 64 + sizeof(int64_t) * (size_t)(N + 1), &d_aux);
+  io.up(d_idx, idx, esz * (size_t)ld * (size_t)k);
   int64_t total = 0;
-  if (e == hipSuccess) {
+  if (io.ok()) {
     double* d_from = (double*)d_out;
     int64_t* d_ptr = (int64_t*)d_aux;
     uint16_t* d_u = (uint16_t*)(d_ptr + N + 1);
     rc = gficf_jaccard_ingest_device(ctx, d_idx, idx_is_f64, N, k, ld, N, (int32_t*)d_table);
     if (!rc) rc = edges_filtered(ctx, (const int32_t*)d_table, N, k, 0, N, d_u, d_ptr, d_from, d_from + E, d_from + 2 * E, 1);
-    if (!rc) e = hipMemcpyAsync(&total, d_ptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
-    if (!rc && e == hipSuccess) {
-      gficf_advise_hugepages(weights, sizeof(double) * 3 * (size_t)E);                         // (a fresh R matrix, first touched by the memset)
-      std::memset(weights, 0, sizeof(double) * 3 * (size_t)E);                                  // NumericMatrix weights(nrow*ncol, 3), :21
-      for (int c = 0; c < 3 && e == hipSuccess && total > 0; ++c)
-        e = hipMemcpyAsync(weights + (size_t)c * (size_t)E, d_from + (size_t)c * (size_t)E, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream);
-      (void)hipStreamSynchronize(ctx->stream);
-    }
+    if (!rc) io.down(&total, d_ptr + N, sizeof(int64_t));
+    rc = io.finish(rc);
+    if (rc) return rc;
+    gficf_advise_hugepages(weights, sizeof(double) * 3 * (size_t)E);                           // (a fresh R matrix, first touched by the memset)
+    std::memset(weights, 0, sizeof(double) * 3 * (size_t)E);                                    // NumericMatrix weights(nrow*ncol, 3), :21
+    for (int c = 0; c < 3; ++c)
+      io.down(weights + (size_t)c * (size_t)E, d_from + (size_t)c * (size_t)E, sizeof(double) * (size_t)total);
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_jaccard_coeff_host: %s", hipGetErrorString(e));
-  return rc;
+  return io.drain(GFICF_OK);                      // (the status word was read above: a plain wait for the three copies)
 }
 
 int gficf_jaccard_filtered_host_finish(gficf_ctx* ctx, double* from, double* to, double* weight) {
   GFICF_CTX_ENTER(ctx);
   gficf_edge_plan* p = ctx->edge_plan;
   if (!p) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "gficf_jaccard_filtered_host_finish without a plan");
-  hipError_t e = hipSuccess;
+  gficf_host_io io{ctx, "gficf_jaccard_filtered_host_finish"};
+  int rc = GFICF_OK;
   if (p->compact && p->n_edges > 0) {
     if (!from || !to || !weight) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL output pointer");
     const size_t b = sizeof(double) * (size_t)p->n_edges;
@@ -1172,14 +1160,13 @@ int gficf_jaccard_filtered_host_finish(gficf_ctx* ctx, double* from, double* to,
     gficf_prefault(from, b);
     gficf_prefault(to, b);
     gficf_prefault(weight, b);
-    e = hipMemcpyAsync(from, p->d_from, b, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(to, p->d_to, b, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(weight, p->d_weight, b, hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
+    io.down(from, p->d_from, b);
+    io.down(to, p->d_to, b);
+    io.down(weight, p->d_weight, b);
+    rc = io.drain(GFICF_OK);
   }
   edge_plan_free(ctx);
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_jaccard_filtered_host_finish: %s", hipGetErrorString(e));
-  return GFICF_OK;
+  return rc;
 }
 
 int gficf_jaccard_host(gficf_ctx* ctx, const void* idx, int idx_is_f64, int64_t N, int k, int64_t ld,

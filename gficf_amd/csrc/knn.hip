@@ -1125,28 +1125,27 @@ int gficf_knn_host(gficf_ctx* ctx, const double* X, int64_t N, int d, int64_t ld
   const size_t xb = sizeof(double) * (size_t)ld * (size_t)d, pb = sizeof(float) * (size_t)N * (size_t)knn_dpad(d);
   const size_t wsb = gficf_knn_workspace_bytes(ctx, N, N, k), ob = (size_t)N * (size_t)k;
   void *d_X = nullptr, *d_P = nullptr, *d_ws = nullptr, *d_out = nullptr;
-  hipError_t e = gficf_pool_get(ctx, 0, xb, &d_X);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 1, pb, &d_P);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 2, wsb, &d_ws);
-  if (e == hipSuccess) e = gficf_pool_get(ctx, 3, ob * (sizeof(int32_t) + sizeof(float)), &d_out);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_X, X, xb, hipMemcpyHostToDevice, ctx->stream);
+  gficf_host_io io{ctx, "gficf_knn_host"};
+  io.get(GFICF_SLOT_STAGE0, xb, &d_X);
+  io.get(GFICF_SLOT_STAGE1, pb, &d_P);
+  io.get(GFICF_SLOT_STAGE2, wsb, &d_ws);
+  io.get(GFICF_SLOT_DEV_SIG_ORDER, ob * (sizeof(int32_t) + sizeof(float)), &d_out);
+  io.up(d_X, X, xb);
   std::vector<float> hd;
-  if (e == hipSuccess) {
+  if (io.ok()) {
     int32_t* d_idx = (int32_t*)d_out;
     float* d_dist = (float*)(d_idx + ob);
     rc = gficf_knn_prepare_device(ctx, d_X, 1, N, d, ld, metric, (float*)d_P);
     if (!rc) rc = gficf_knn_search_device(ctx, (const float*)d_P, N, d, k, metric, 0, N, d_ws, wsb, d_idx, dist ? d_dist : nullptr, N);
     gficf_advise_hugepages(idx, ob * sizeof(int32_t));             // (fresh R matrices: first touched by the copies below)
     if (dist) gficf_advise_hugepages(dist, ob * sizeof(double));
-    if (!rc) e = hipMemcpyAsync(idx, d_idx, ob * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess && dist) {
+    if (!rc) io.down(idx, d_idx, ob * sizeof(int32_t));
+    if (!rc && io.ok() && dist) {
       hd.resize(ob);
-      e = hipMemcpyAsync(hd.data(), d_dist, ob * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+      io.down(hd.data(), d_dist, ob * sizeof(float));
     }
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_knn_host: %s", hipGetErrorString(e));
+  rc = io.finish(rc);
   if (rc) return rc;
   if (dist)
     for (size_t t = 0; t < ob; ++t) dist[t] = (double)hd[t];

@@ -1805,32 +1805,28 @@ int gficf_louvain_host(gficf_ctx* ctx, int64_t N, const void* indptr, int indptr
   if (modularity) *modularity = 0.0;
   if (N == 0) return GFICF_OK;
   if (!indptr || !labels || !n_clusters) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
-  std::vector<int64_t> h_ptr((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c) h_ptr[(size_t)c] = indptr_is_i64 ? ((const int64_t*)indptr)[c] : (int64_t)((const int32_t*)indptr)[c];
-  bool mono = h_ptr[0] == 0;
-  for (int64_t c = 0; c < N && mono; ++c) mono = h_ptr[(size_t)c + 1] >= h_ptr[(size_t)c];
-  const int64_t nnz = h_ptr[(size_t)N];
-  if (!mono) GFICF_FAIL(GFICF_ERR_BAD_CSC, "indptr does not start at 0 or is not monotone");
+  std::vector<int64_t> h_ptr;
+  int64_t nnz = 0;
+  int rc = gficf_host_colptr(indptr, indptr_is_i64, N, "indptr", h_ptr, &nnz);
+  if (rc) return rc;
   if (nnz > 0 && (!indices || !x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const size_t nsz = (size_t)(nnz > 0 ? nnz : 1), wsb = gficf_louvain_workspace_bytes(N, nnz, n_start);
-  gficf_arena ar;                                   // pool slot 0: no allocation per call
-  const size_t o_ptr = ar.take(sizeof(int64_t) * ((size_t)N + 1)), o_idx = ar.take(sizeof(int32_t) * nsz), o_x = ar.take(sizeof(double) * nsz);
-  const size_t o_lab = ar.take(sizeof(int32_t) * (size_t)N), o_ws = ar.take(wsb);
-  hipError_t e = ar.bind(ctx, 0);
-  int64_t* const d_ptr = ar.at<int64_t>(o_ptr); int32_t* const d_idx = ar.at<int32_t>(o_idx); double* const d_x = ar.at<double>(o_x);
-  int32_t* const d_lab = ar.at<int32_t>(o_lab); void* const d_ws = ar.at<void>(o_ws);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ptr, h_ptr.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  int rc = GFICF_OK;
-  if (e == hipSuccess) {
-    rc = gficf_louvain_device(ctx, N, d_ptr, d_idx, d_x, nnz, resolution, algorithm, n_start, n_iter, seed, d_lab, n_clusters, modularity, d_ws, wsb);
-    if (!rc) e = hipMemcpyAsync(labels, d_lab, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+  gficf_host_io io{ctx, "gficf_louvain_host"};
+  gficf_carver cv;
+  int64_t* d_ptr; int32_t *d_idx, *d_lab; double* d_x; void* d_ws;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_ptr = cv.take<int64_t>((size_t)N + 1); d_idx = cv.take<int32_t>(nsz); d_x = cv.take<double>(nsz);
+    d_lab = cv.take<int32_t>((size_t)N); d_ws = cv.take<char>(wsb);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_louvain_host: %s", hipGetErrorString(e));
-  return rc;
+  io.up(d_ptr, h_ptr.data(), sizeof(int64_t) * ((size_t)N + 1));
+  io.up(d_idx, indices, sizeof(int32_t) * (size_t)nnz);
+  io.up(d_x, x, sizeof(double) * (size_t)nnz);
+  if (io.ok()) {
+    rc = gficf_louvain_device(ctx, N, d_ptr, d_idx, d_x, nnz, resolution, algorithm, n_start, n_iter, seed, d_lab, n_clusters, modularity, d_ws, wsb);
+    if (!rc) io.down(labels, d_lab, sizeof(int32_t) * (size_t)N);
+  }
+  return io.finish(rc);
 }
 
 }  // extern "C"

@@ -500,47 +500,39 @@ int gficf_cluster_markers_host(gficf_ctx* ctx, int64_t G, int64_t N, const void*
   GFICF_CTX_ENTER(ctx);
   if (G < 0 || N < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "negative size");
   if (!colptr || !cluster || (G > 0 && (!p || !lfc))) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
-  std::vector<int64_t> cp((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c) cp[(size_t)c] = colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c];
-  if (cp[0] != 0) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr[0] != 0");
-  for (int64_t c = 0; c < N; ++c)
-    if (cp[(size_t)c + 1] < cp[(size_t)c]) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr not monotone at cell %lld", (long long)c);
-  const int64_t nnz = cp[(size_t)N];
-  int rc = mk_check_sizes(G, N, nnz, C);
+  std::vector<int64_t> cp;
+  int64_t nnz = 0;
+  int rc = gficf_host_colptr(colptr, colptr_is_i64, N, "colptr", cp, &nnz);
+  if (rc) return rc;
+  rc = mk_check_sizes(G, N, nnz, C);
   if (rc) return rc;
   if (nnz > 0 && (!rowidx || !x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   rc = mk_check_labels(cluster, N, C);
   if (rc) return rc;
   const size_t nsz = (size_t)(nnz > 0 ? nnz : 1), gc = (size_t)G * (size_t)C;
   const size_t wsb = gficf_cluster_markers_workspace_bytes(G, N, nnz, C);
-  gficf_arena ar;                                          // pool slot 0
-  const size_t o_cp = ar.take(sizeof(int64_t) * ((size_t)N + 1)), o_ri = ar.take(sizeof(int32_t) * nsz), o_x = ar.take(sizeof(double) * nsz);
-  const size_t o_cl = ar.take(sizeof(int32_t) * (size_t)N), o_p = ar.take(sizeof(double) * gc), o_l = ar.take(sizeof(double) * gc);
-  const size_t o_ws = ar.take(wsb);
-  hipError_t e = ar.bind(ctx, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(ar.at<int64_t>(o_cp), cp.data(), sizeof(int64_t) * cp.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(ar.at<int32_t>(o_ri), rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(ar.at<double>(o_x), x, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(ar.at<int32_t>(o_cl), cluster, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(ctx->stream);
-    GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_cluster_markers_host: %s", hipGetErrorString(e));
+  gficf_host_io io{ctx, "gficf_cluster_markers_host"};
+  gficf_carver cv;
+  int64_t* d_cp; int32_t *d_ri, *d_cl; double *d_x, *d_p, *d_l; char* d_ws;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_cp = cv.take<int64_t>((size_t)N + 1); d_ri = cv.take<int32_t>(nsz); d_x = cv.take<double>(nsz);
+    d_cl = cv.take<int32_t>((size_t)N); d_p = cv.take<double>(gc); d_l = cv.take<double>(gc);
+    d_ws = cv.take<char>(wsb);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);
   }
-  rc = gficf_cluster_markers_device(ctx, G, N, ar.at<int64_t>(o_cp), ar.at<int32_t>(o_ri), ar.at<double>(o_x), nnz, ar.at<int32_t>(o_cl), C,
-                                    ar.at<char>(o_ws), wsb, ar.at<double>(o_p), ar.at<double>(o_l));
-  if (rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  if (gc) {
-    e = hipMemcpyAsync(p, ar.at<double>(o_p), sizeof(double) * gc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(lfc, ar.at<double>(o_l), sizeof(double) * gc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->stream);
-      GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_cluster_markers_host: %s", hipGetErrorString(e));
+  io.up(d_cp, cp.data(), sizeof(int64_t) * cp.size());
+  io.up(d_ri, rowidx, sizeof(int32_t) * (size_t)nnz);
+  io.up(d_x, x, sizeof(double) * (size_t)nnz);
+  io.up(d_cl, cluster, sizeof(int32_t) * (size_t)N);
+  if (io.ok()) {
+    rc = gficf_cluster_markers_device(ctx, G, N, d_cp, d_ri, d_x, nnz, d_cl, C, d_ws, wsb, d_p, d_l);
+    if (!rc) {
+      io.down(p, d_p, sizeof(double) * gc);
+      io.down(lfc, d_l, sizeof(double) * gc);
     }
   }
-  return gficf_cluster_markers_sync(ctx, ar.at<char>(o_ws));
+  if (!io.ok() || rc) return io.drain(rc);
+  return gficf_cluster_markers_sync(ctx, d_ws);
 }
 
 int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, const double* X, int64_t n2, const double* Y, double* out) {
@@ -555,16 +547,18 @@ int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, cons
   if ((double)G * (double)N > (double)UINT32_MAX - 2) GFICF_FAIL(GFICF_ERR_UNSUPPORTED, "more than 2^32 - 2 entries");
   hipStream_t st = ctx->stream;
   const int64_t nch = gficf_ceil_div(N, MK_DENSE_CHUNK);
-  gficf_arena ar;                                          // pool slot 0: the inputs and the count matrix; slot 1: the workspace
-  const size_t o_x = ar.take(sizeof(double) * (size_t)(G * n1)), o_y = ar.take(sizeof(double) * (size_t)(G * n2));
-  const size_t o_cnt = ar.take(sizeof(int64_t) * (size_t)(G * nch + 1)), o_cl = ar.take(sizeof(int32_t) * (size_t)N);
-  const size_t o_p = ar.take(sizeof(double) * (size_t)G * 2), o_l = ar.take(sizeof(double) * (size_t)G * 2);
-  GFICF_HIP_CHECK(ar.bind(ctx, 0));
-  const double *dX = ar.at<double>(o_x), *dY = ar.at<double>(o_y);
-  int64_t* const cnt = ar.at<int64_t>(o_cnt);
-  int32_t* const dcl = ar.at<int32_t>(o_cl);
-  GFICF_HIP_CHECK(hipMemcpyAsync(ar.at<double>(o_x), X, sizeof(double) * (size_t)(G * n1), hipMemcpyHostToDevice, st));
-  GFICF_HIP_CHECK(hipMemcpyAsync(ar.at<double>(o_y), Y, sizeof(double) * (size_t)(G * n2), hipMemcpyHostToDevice, st));
+  gficf_host_io io{ctx, "gficf_cluster_markers_dense_host"};
+  gficf_carver cv;                                         // STAGE0: the inputs, the count matrix and the results; STAGE1: the workspace
+  double *dX, *dY, *dp, *dl; int64_t* cnt; int32_t* dcl;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    dX = cv.take<double>((size_t)(G * n1)); dY = cv.take<double>((size_t)(G * n2));
+    cnt = cv.take<int64_t>((size_t)(G * nch + 1)); dcl = cv.take<int32_t>((size_t)N);
+    dp = cv.take<double>((size_t)G * 2); dl = cv.take<double>((size_t)G * 2);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);
+  }
+  io.up(dX, X, sizeof(double) * (size_t)(G * n1));
+  io.up(dY, Y, sizeof(double) * (size_t)(G * n2));
+  if (!io.ok()) return io.drain(GFICF_OK);
   GFICF_HIP_CHECK(hipMemsetAsync(cnt + G * nch, 0, sizeof(int64_t), st));
   hipLaunchKernelGGL(k_mk_dense<false>, dim3(mk_grid(G * nch)), dim3(256), 0, st, G, n1, n2, dX, dY, nch, cnt, (int32_t*)nullptr, (double*)nullptr);
   GFICF_HIP_CHECK(hipGetLastError());
@@ -575,7 +569,7 @@ int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, cons
   GFICF_HIP_CHECK(hipStreamSynchronize(st));
   const size_t wsb = gficf_cluster_markers_workspace_bytes(G, N, nnz, 2);
   void* wsp = nullptr;
-  GFICF_HIP_CHECK(gficf_pool_get(ctx, 1, wsb, &wsp));
+  GFICF_HIP_CHECK(gficf_pool_get(ctx, GFICF_SLOT_STAGE1, wsb, &wsp));
   MkWs w;
   mk_carve((char*)wsp, G, N, nnz, 2, w);
   GFICF_HIP_CHECK(hipMemsetAsync(w.status, 0, sizeof(uint32_t), st));
@@ -584,15 +578,12 @@ int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, cons
   hipLaunchKernelGGL(k_mk_dense_ptr, dim3(mk_grid((G > N ? G : N) + 1)), dim3(256), 0, st, G, nch, n1, N, (const int64_t*)cnt, w.tptr, dcl);
   hipLaunchKernelGGL(k_mk_labels, dim3(mk_grid(N)), dim3(256), 0, st, N, (const int32_t*)dcl, 2, w.ncl, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
-  double *dp = ar.at<double>(o_p), *dl = ar.at<double>(o_l);
   rc = mk_core(ctx, w, G, N, nnz, dcl, 2, dp, dl);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
+  if (!rc) {                                     // out = [p, log2FC] of the first sample (cluster 0): column 0 of each G x 2 result
+    io.down(out, dp, sizeof(double) * (size_t)G);
+    io.down(out + G, dl, sizeof(double) * (size_t)G);
   }
-  // out = [p, log2FC] of the first sample (cluster 0): column 0 of each G x 2 result
-  GFICF_HIP_CHECK(hipMemcpyAsync(out, dp, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, st));
-  GFICF_HIP_CHECK(hipMemcpyAsync(out + G, dl, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, st));
+  if (!io.ok() || rc) return io.drain(rc);
   return gficf_cluster_markers_sync(ctx, w.status);
 }
 

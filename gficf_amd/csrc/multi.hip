@@ -36,7 +36,7 @@ struct gficf_multi_block {
   int64_t b = 0, e = 0;            // cells [b, e)
   int64_t p0 = 0, p1 = 0;          // stored entries [p0, p1) (GF-ICF)
   int64_t nnz_kept = 0, out_off = 0;
-  // plan state (device pointers into pool slot 4 of the block's context)
+  // plan state (device pointers into GFICF_SLOT_GFICF_PLAN of the block's context)
   int64_t* d_colptr = nullptr;
   int32_t* d_rowidx = nullptr;
   double* d_x = nullptr;
@@ -178,7 +178,7 @@ int gficf_multi_cell_blocks(int64_t N, int ndev, int64_t* bounds) {
  * r + 1 equal shares of the entries (gficf_amd/dist.py: shard_bounds_by_nnz).  bounds: ndev + 1 entries. */
 int gficf_multi_cell_blocks_by_nnz(int64_t N, const void* colptr, int colptr_is_i64, int ndev, int64_t* bounds) {
   if (N < 0 || ndev < 1 || !bounds || !colptr) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "N < 0, ndev < 1 or a NULL pointer");
-  auto cp = [&](int64_t c) -> int64_t { return colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c]; };
+  auto cp = [&](int64_t c) -> int64_t { return gficf_colptr_at(colptr, colptr_is_i64, c); };
   const int64_t base = cp(0), nnz = N > 0 ? cp(N) - base : 0;
   bounds[0] = 0;
   for (int r = 1; r < ndev; ++r) {
@@ -305,9 +305,9 @@ int gficf_jaccard_host_multi(gficf_multi* m, const void* idx, int idx_is_f64, in
       const int64_t n = bd[r + 1] - bd[r];
       hipError_t e = hipSetDevice(m->dev[r]);
       const int64_t rows_up = m->peer ? n : N, row0 = m->peer ? bd[r] : 0;
-      if (e == hipSuccess) e = gficf_pool_get(c, 0, esz * (size_t)(rows_up > 0 ? rows_up : 1) * (size_t)k, &d_idx[r]);
-      if (e == hipSuccess) e = gficf_pool_get(c, 1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table[r]);
-      if (e == hipSuccess) e = gficf_pool_get(c, 2, sizeof(double) * 3 * (size_t)(n > 0 ? n : 1) * (size_t)k, (void**)&d_out[r]);
+      if (e == hipSuccess) e = gficf_pool_get(c, GFICF_SLOT_STAGE0, esz * (size_t)(rows_up > 0 ? rows_up : 1) * (size_t)k, &d_idx[r]);
+      if (e == hipSuccess) e = gficf_pool_get(c, GFICF_SLOT_STAGE1, sizeof(int32_t) * (size_t)N * (size_t)roww, (void**)&d_table[r]);
+      if (e == hipSuccess) e = gficf_pool_get(c, GFICF_SLOT_STAGE2, sizeof(double) * 3 * (size_t)(n > 0 ? n : 1) * (size_t)k, (void**)&d_out[r]);
       if (e == hipSuccess && rows_up > 0)     // k columns of rows_up ids out of the column-major matrix (leading dimension ld)
         e = hipMemcpy2DAsync(d_idx[r], esz * (size_t)rows_up, (const char*)idx + esz * (size_t)row0, esz * (size_t)ld, esz * (size_t)rows_up,
                              (size_t)k, hipMemcpyHostToDevice, m->stream[r]);
@@ -685,13 +685,9 @@ int gficf_normalize_csc_host_multi_plan(gficf_multi* m, int64_t G, int64_t N, co
   if (G > 0x7FFFFFFFll) GFICF_FAIL(GFICF_ERR_UNSUPPORTED, "G = %lld exceeds int32 row indices", (long long)G);
   if (!colptr || !G_kept || !nnz_kept) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   multi_plan_clear(m);
-  std::vector<int64_t> cp((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c)
-    cp[(size_t)c] = colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c];
-  if (cp[0] != 0) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr[0] = %lld, expected 0", (long long)cp[0]);
-  for (int64_t c = 0; c < N; ++c)
-    if (cp[(size_t)c + 1] < cp[(size_t)c]) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr not monotone at cell %lld", (long long)c);
-  const int64_t nnz = cp[(size_t)N];
+  std::vector<int64_t> cp;
+  int64_t nnz = 0;
+  { const int crc = gficf_host_colptr(colptr, colptr_is_i64, N, "colptr", cp, &nnz); if (crc) return crc; }
   if (nnz > 0 && (!rowidx || !x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const int P = m->ndev;
   std::vector<int64_t> bd((size_t)P + 1);
@@ -711,18 +707,17 @@ int gficf_normalize_csc_host_multi_plan(gficf_multi* m, int64_t G, int64_t N, co
     for (int64_t t = 0; t <= n; ++t) cpl[r][(size_t)t] = cp[(size_t)(B.b + t)] - B.p0;      // the block's colptr starts at 0
     ntl[r].assign(gsz, 0);
     hipError_t e = hipSetDevice(m->dev[r]);
-    gficf_arena ar;
+    gficf_carver cv;
     const size_t nsz = (size_t)(nz > 0 ? nz : 1);
-    const size_t o_cp = ar.take(sizeof(int64_t) * ((size_t)n + 1)), o_ri = ar.take(sizeof(int32_t) * nsz), o_x = ar.take(sizeof(double) * nsz);
-    const size_t o_nt = ar.take(sizeof(int64_t) * gsz), o_keep = ar.take(gsz), o_genes = ar.take(gficf_csc_genes_bytes(G));
-    const size_t o_w = ar.take(sizeof(double) * gsz), o_gk = ar.take(sizeof(int64_t)), o_ocp = ar.take(sizeof(int64_t) * ((size_t)n + 1));
-    const size_t o_win = ar.take(sizeof(double) * gsz);
-    if (e == hipSuccess) e = ar.bind(c, 4);
+    for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
+      B.d_colptr = cv.take<int64_t>((size_t)n + 1); B.d_rowidx = cv.take<int32_t>(nsz); B.d_x = cv.take<double>(nsz);
+      B.d_nt = cv.take<int64_t>(gsz); B.d_keep = cv.take<uint8_t>(gsz); B.d_genes = (gficf_gene_entry*)cv.take<char>(gficf_csc_genes_bytes(G));
+      B.d_w = cv.take<double>(gsz); B.d_gkept = cv.take<int64_t>(1); B.d_out_colptr = cv.take<int64_t>((size_t)n + 1);
+      B.d_w_in = cv.take<double>(gsz);
+      if (pass == 0) e = cv.bind(c, GFICF_SLOT_GFICF_PLAN);
+    }
     if (e != hipSuccess) return hip_fail("device buffers of the GF-ICF block", e);
-    B.d_colptr = ar.at<int64_t>(o_cp); B.d_rowidx = ar.at<int32_t>(o_ri); B.d_x = ar.at<double>(o_x);
-    B.d_nt = ar.at<int64_t>(o_nt); B.d_keep = ar.at<uint8_t>(o_keep); B.d_genes = ar.at<gficf_gene_entry>(o_genes);
-    B.d_w = ar.at<double>(o_w); B.d_gkept = ar.at<int64_t>(o_gk); B.d_out_colptr = ar.at<int64_t>(o_ocp);
-    B.d_w_in = (w_in && G > 0) ? ar.at<double>(o_win) : nullptr;
+    if (!(w_in && G > 0)) B.d_w_in = nullptr;
     hipStream_t st = m->stream[r];
     e = hipMemcpyAsync(B.d_colptr, cpl[r].data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && nz > 0) e = hipMemcpyAsync(B.d_rowidx, rowidx + B.p0, sizeof(int32_t) * (size_t)nz, hipMemcpyHostToDevice, st);
@@ -800,12 +795,13 @@ int gficf_normalize_csc_host_multi_finish(gficf_multi* m, uint8_t* keep, int64_t
     hipStream_t st = m->stream[r];
     hipError_t e = hipSetDevice(m->dev[r]);
     const size_t ksz = (size_t)(B.nnz_kept > 0 ? B.nnz_kept : 1);
-    gficf_arena ar;
-    const size_t o_ri = ar.take(sizeof(int32_t) * ksz), o_x = ar.take(sizeof(double) * ksz);
-    if (e == hipSuccess) e = ar.bind(c, 7);
+    gficf_carver cv;
+    int32_t* d_ori = nullptr; double* d_ox = nullptr;
+    for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
+      d_ori = cv.take<int32_t>(ksz); d_ox = cv.take<double>(ksz);
+      if (pass == 0) e = cv.bind(c, GFICF_SLOT_GFICF_OUT);
+    }
     if (e != hipSuccess) return hip_fail("output buffers of the GF-ICF block", e);
-    int32_t* const d_ori = ar.at<int32_t>(o_ri);
-    double* const d_ox = ar.at<double>(o_x);
     const int rc = gficf_csc_scale_device(c, G, n, B.d_colptr, B.d_rowidx, B.d_x, nz, B.d_genes, B.d_gkept, B.d_out_colptr, d_ori, d_ox);
     if (rc) return rc;
     ocp[r].resize((size_t)n + 1);

@@ -96,7 +96,7 @@ extern "C" int gficf_phenograph_host(gficf_ctx* ctx, const double* X, int64_t N,
     }
     if (pass == 0) {
       void* blk = nullptr;
-      const hipError_t e0 = gficf_pool_get(ctx, 0, cv.total(), &blk);
+      const hipError_t e0 = gficf_pool_get(ctx, GFICF_SLOT_STAGE0, cv.total(), &blk);
       if (e0 != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_phenograph_host: %s", hipGetErrorString(e0));
       cv.base = (char*)blk;
     }
@@ -156,7 +156,7 @@ extern "C" int gficf_phenograph_host(gficf_ctx* ctx, const double* X, int64_t N,
   // communities
   const size_t lws = gficf_louvain_workspace_bytes(N, h_cnt[1], n_start);      // all the starts in one launch set
   void* d_lws = nullptr;
-  e = gficf_pool_get(ctx, 1, lws, &d_lws);
+  e = gficf_pool_get(ctx, GFICF_SLOT_STAGE1, lws, &d_lws);
   if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_phenograph_host: %s", hipGetErrorString(e));
   rc = gficf_louvain_device(ctx, N, (const int64_t*)d_indptr, (const int32_t*)d_indices, (const double*)d_ax, h_cnt[1], resolution, algorithm,
                             n_start, n_iter, seed, (int32_t*)d_lab, n_clusters, modularity, d_lws, lws);

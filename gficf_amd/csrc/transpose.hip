@@ -295,44 +295,39 @@ int gficf_csc_transpose_host(gficf_ctx* ctx, int64_t G, int64_t N, const void* c
   GFICF_CTX_ENTER(ctx);
   if (G < 0 || N < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "negative size");
   if (!colptr || !out_ptr) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
-  std::vector<int64_t> h_cp((size_t)N + 1);
-  for (int64_t c = 0; c <= N; ++c) h_cp[(size_t)c] = colptr_is_i64 ? ((const int64_t*)colptr)[c] : (int64_t)((const int32_t*)colptr)[c];
-  bool mono = h_cp[0] == 0;
-  for (int64_t c = 0; c < N && mono; ++c) mono = h_cp[(size_t)c + 1] >= h_cp[(size_t)c];
-  const int64_t nnz = h_cp[(size_t)N];
-  if (!mono) GFICF_FAIL(GFICF_ERR_BAD_CSC, "colptr does not start at 0 or is not monotone");
+  std::vector<int64_t> h_cp;
+  int64_t nnz = 0;
+  int rc = gficf_host_colptr(colptr, colptr_is_i64, N, "colptr", h_cp, &nnz);
+  if (rc) return rc;
   if (nnz > 0 && (!rowidx || !x || !out_idx || !out_x)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const size_t nsz = (size_t)(nnz > 0 ? nnz : 1), wsb = gficf_csc_transpose_workspace_bytes(G, N);
-  gficf_arena ar;                                   // pool slot 0: no allocation per call
-  const size_t o_cp = ar.take(sizeof(int64_t) * ((size_t)N + 1)), o_op = ar.take(sizeof(int64_t) * ((size_t)G + 1));
-  const size_t o_ri = ar.take(sizeof(int32_t) * nsz), o_oi = ar.take(sizeof(int32_t) * nsz);
-  const size_t o_x = ar.take(sizeof(double) * nsz), o_ox = ar.take(sizeof(double) * nsz), o_ws = ar.take(wsb);
-  hipError_t e = ar.bind(ctx, 0);
-  int64_t* const d_cp = ar.at<int64_t>(o_cp); int64_t* const d_op = ar.at<int64_t>(o_op);
-  int32_t* const d_ri = ar.at<int32_t>(o_ri); int32_t* const d_oi = ar.at<int32_t>(o_oi);
-  double* const d_x = ar.at<double>(o_x); double* const d_ox = ar.at<double>(o_ox);
-  void* const d_ws = ar.at<void>(o_ws);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cp, h_cp.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_ri, rowidx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-  int rc = GFICF_OK;
-  if (e == hipSuccess) {
+  gficf_host_io io{ctx, "gficf_csc_transpose_host"};
+  gficf_carver cv;
+  int64_t *d_cp, *d_op; int32_t *d_ri, *d_oi; double *d_x, *d_ox; void* d_ws;
+  for (int pass = 0; pass < 2 && io.ok(); ++pass) {
+    d_cp = cv.take<int64_t>((size_t)N + 1); d_op = cv.take<int64_t>((size_t)G + 1);
+    d_ri = cv.take<int32_t>(nsz); d_oi = cv.take<int32_t>(nsz);
+    d_x = cv.take<double>(nsz); d_ox = cv.take<double>(nsz);
+    d_ws = cv.take<char>(wsb);
+    if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);
+  }
+  io.up(d_cp, h_cp.data(), sizeof(int64_t) * ((size_t)N + 1));
+  io.up(d_ri, rowidx, sizeof(int32_t) * (size_t)nnz);
+  io.up(d_x, x, sizeof(double) * (size_t)nnz);
+  if (io.ok()) {
     rc = gficf_csc_transpose_device(ctx, G, N, d_cp, d_ri, d_x, nnz, d_op, d_oi, d_ox, d_ws, wsb);
     if (!rc && nnz > 0) {                          // map the caller's fresh result pages while the kernels run
       gficf_prefault(out_x, sizeof(double) * (size_t)nnz);
       gficf_prefault(out_idx, sizeof(int32_t) * (size_t)nnz);
     }
-    // validate (status word) before the results are handed back
-    if (!rc) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
-    if (!rc) e = hipMemcpyAsync(out_ptr, d_op, sizeof(int64_t) * ((size_t)G + 1), hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess && nnz > 0) e = hipMemcpyAsync(out_idx, d_oi, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess && nnz > 0) e = hipMemcpyAsync(out_x, d_ox, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) rc = gficf_ctx_sync(ctx);
-    else (void)hipStreamSynchronize(ctx->stream);
+    rc = io.finish(rc);                            // validate (status word) before the results are handed back
+    if (!rc) {
+      io.down(out_ptr, d_op, sizeof(int64_t) * ((size_t)G + 1));
+      io.down(out_idx, d_oi, sizeof(int32_t) * (size_t)nnz);
+      io.down(out_x, d_ox, sizeof(double) * (size_t)nnz);
+    }
   }
-  if (e != hipSuccess) GFICF_FAIL(GFICF_ERR_HIP, "HIP failure in gficf_csc_transpose_host: %s", hipGetErrorString(e));
-  return rc;
+  return io.finish(rc);
 }
 
 }  // extern "C"

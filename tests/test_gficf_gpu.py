@@ -836,3 +836,124 @@ def test_gficf_against_the_closed_form_of_a_circulant_matrix(G, N, s, n_rare):
     # every cell has unit L2 norm (R/gficf.R:100-103) — a property, checked on the result itself
     sq = np.add.reduceat(got.data ** 2, got.indptr[:-1])
     assert np.allclose(sq, 1.0, rtol=1e-12)
+
+
+# ---- the column pointer of every host entry that takes one goes through one check (gficf_host_colptr)
+_CP_G, _CP_N, _CP_C, _SENTINEL = 40, 30, 4, -7
+
+
+def _cp_valid(entry):
+    """(G, N, column pointer, row index, values) of a small valid matrix: counts for the CSC entries, a ring of 8 cliques for Louvain."""
+    if entry == "louvain":
+        from tests.helpers import closed_form
+
+        A, _ = closed_form.ring_of_cliques(8, 5, 1.0)
+        return A.shape[0], A.shape[0], A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64)
+    cp, ri, x = synth.counts_csc(_CP_G, _CP_N, seed=19)
+    return _CP_G, _CP_N, cp.astype(np.int64), ri.astype(np.int32), x.astype(np.float64)
+
+
+def _cp_call(entry, G, N, colptr, ri, x):
+    """The raw C entry with sentinel-filled outputs: (status code, the output arrays)."""
+    import ctypes
+
+    from gficf_amd import _lib, _markers_lib, api
+
+    L, h = _lib.load(), api.default_context().handle
+    ptr, is64 = api._np_ptr, 1 if colptr.dtype == np.int64 else 0
+    ids = np.ascontiguousarray(np.arange(max(N, 1)) % _CP_C, dtype=np.int32)
+    if entry in ("normalize_plan", "multi_plan"):
+        gk, nk = ctypes.c_int64(_SENTINEL), ctypes.c_int64(_SENTINEL)
+        fn, hh = (L.gficf_normalize_csc_host_plan, h) if entry == "normalize_plan" else (L.gficf_normalize_csc_host_multi_plan, api._multi([0]).handle)
+        rc = fn(hh, G, N, ptr(colptr), is64, ptr(ri), ptr(x), 0.05, 1.0, None, ctypes.byref(gk), ctypes.byref(nk))
+        return rc, [np.array([gk.value, nk.value])]
+    if entry == "signatures":
+        out = np.full((_CP_C, G), float(_SENTINEL))
+        return L.gficf_cluster_signatures_host(h, G, N, ptr(colptr), is64, ptr(ri), ptr(x), ptr(ids), _CP_C, ptr(out)), [out]
+    if entry == "transpose":
+        outs = [np.full(G + 1, _SENTINEL, dtype=np.int64), np.full(len(ri), _SENTINEL, dtype=np.int32), np.full(len(ri), float(_SENTINEL))]
+        return L.gficf_csc_transpose_host(h, G, N, ptr(colptr), is64, ptr(ri), ptr(x), *[ptr(o) for o in outs]), outs
+    if entry == "markers":
+        outs = [np.full((_CP_C, G), float(_SENTINEL)), np.full((_CP_C, G), float(_SENTINEL))]
+        return _markers_lib.load().gficf_cluster_markers_host(h, G, N, ptr(colptr), is64, ptr(ri), ptr(x), ptr(ids), _CP_C, ptr(outs[0]), ptr(outs[1])), outs
+    assert entry == "louvain"
+    labels, nc, q = np.full(max(N, 1), _SENTINEL, dtype=np.int32), ctypes.c_int64(0), ctypes.c_double(0.0)
+    rc = L.gficf_louvain_host(h, N, ptr(colptr), is64, ptr(ri), ptr(x), 0.8, 1, 3, 10, 7, ptr(labels), ctypes.byref(nc), ctypes.byref(q))
+    return rc, [labels, np.array([nc.value]), np.array([q.value])]
+
+
+def _cp_check_valid(entry, width):
+    """The same entry on the valid matrix, column pointer of the same width: the result the feature's own tests expect."""
+    from gficf_amd import _lib, api
+    from oracle import oracle_np
+
+    G, N, cp, ri, x = _cp_valid(entry)
+    cpw = cp.astype(width)
+    if entry == "louvain":
+        from tests.helpers import closed_form
+
+        rc, (labels, nc, q) = _cp_call(entry, G, N, cpw, ri, x)
+        clique = np.repeat(np.arange(8), 5)
+        assert rc == 0 and nc[0] == 8 and len(set(labels)) == 8 and len(set(zip(labels.tolist(), clique.tolist()))) == 8
+        assert abs(q[0] - closed_form.ring_of_cliques_modularity(8, 5, 0.8)) < 1e-9
+        return
+    M, Mref = sp.csc_matrix((x, ri, cp), shape=(G, N)), sp.csc_matrix((x, ri, cp), shape=(G, N))
+    M.indptr = cpw                                       # (the constructor narrows the index type where the values fit)
+    lab = np.arange(N) % _CP_C
+    if entry in ("normalize_plan", "multi_plan"):
+        L = _lib.load()
+        if entry == "normalize_plan":
+            _, keep, nt, w, out = api._normalize_csc_host_run(L, api.default_context(), M, cpw, ri, x, G, N, 0.05, 1.0, None)
+        else:
+            _, keep, nt, w, out = api._normalize_csc_host_run(L, api._multi([0]), M, cpw, ri, x, G, N, 0.05, 1.0, None,
+                                                              L.gficf_normalize_csc_host_multi_plan, L.gficf_normalize_csc_host_multi_finish)
+        check_against_oracle({"genes": np.flatnonzero(keep), "nt": nt[keep], "w": w[keep], "gficf": out}, oracle.gficf_csc(G, N, cp, ri, x, 0.05, 1.0), N)
+    elif entry == "signatures":
+        got, labels = gficf_amd.cluster_signatures(M, lab)
+        want, wl = oracle_np.cluster_signatures_np(Mref, lab)
+        assert list(labels) == list(wl) and np.abs(got - want).max() < 1e-10
+    elif entry == "transpose":
+        T = gficf_amd.transpose_gficf(M)
+        tp, ti, tv = oracle_np.transpose_np(G, N, cp, ri, x)
+        assert np.array_equal(T.indptr, tp) and np.array_equal(T.indices, ti) and np.array_equal(T.data, tv)
+    else:
+        from tests.helpers import markers_np as mk
+
+        P, LFC, labels = gficf_amd.cluster_markers(M, lab)
+        ref = mk.markers_sparse(Mref, lab.astype(np.int32), _CP_C)
+        rp, rl = ref["p"][:, [int(l) for l in labels]], ref["lfc"][:, [int(l) for l in labels]]
+        one = rp == 1.0
+        assert np.array_equal(P[one], rp[one]) and np.allclose(P[~one], rp[~one], rtol=1e-12, atol=0)
+        assert np.abs(LFC - rl).max(initial=0) <= 1e-10
+
+
+_CP_ENTRIES = ["normalize_plan", "signatures", "transpose", "louvain", "markers", "multi_plan"]
+
+
+@pytest.mark.parametrize("entry,width,case", [(e, w, c) for e in _CP_ENTRIES for w in (np.int32, np.int64)
+                                              for c in ("first_is_1", "decreases", "empty_first_is_1")
+                                              if not (e == "louvain" and c == "empty_first_is_1")])
+def test_host_entries_reject_a_malformed_column_pointer(entry, width, case):
+    """Every host entry that takes a column pointer, both widths: a pointer that starts at 1, one that decreases in the middle, and
+    N == 0 with a first entry of 1 are GFICF_ERR_BAD_CSC, nothing is written to the outputs, and the context stays usable (the same
+    entry on a valid matrix then gives the expected result).  The pointer is refused on the host before anything is enqueued.
+    Louvain returns GFICF_OK for N == 0 before it reads the pointer (no third case), and resets n_clusters / modularity on entry.
+    `signatures-*-empty_first_is_1` failed before the entries shared one check: that entry tested colptr[0] inside its loop over cells."""
+    from gficf_amd import _lib
+
+    G, N, cp, ri, x = _cp_valid(entry)
+    if case == "first_is_1":
+        bad = cp + 1
+    elif case == "decreases":
+        bad = cp.copy()
+        assert bad[N // 2 - 1] >= 1
+        bad[N // 2] = bad[N // 2 - 1] - 1
+    else:
+        N, bad = 0, np.array([1])
+    rc, outs = _cp_call(entry, G, N, np.ascontiguousarray(bad.astype(width)), ri, x)
+    assert _lib.STATUS_NAMES[rc] == "GFICF_ERR_BAD_CSC", (rc, _lib.last_error())
+    if entry == "louvain":
+        assert (outs[0] == _SENTINEL).all() and outs[1][0] == 0 and outs[2][0] == 0.0
+    else:
+        assert all((o == _SENTINEL).all() for o in outs)
+    _cp_check_valid(entry, width)
