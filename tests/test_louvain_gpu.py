@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 import scipy.sparse as sp
+from scipy.sparse import csgraph
 
 import gficf_amd
 from oracle import oracle_np
@@ -47,6 +48,15 @@ def check_labels(A, lab, res):
     sizes = np.bincount(lab, minlength=lab.n_clusters)
     assert (sizes > 0).all() and (np.diff(sizes) <= 0).all()                 # orderClustersByNNodes
     assert abs(lab.modularity - oracle_np.modularity_np(A, lab, res)) < 1e-9
+    # exact, whatever the optimum: a vertex only ever joins a community it has an edge to, or leaves for its own id, so no cluster spans two
+    # connected components of the graph (off-diagonal, positive entries), and a vertex without an edge is alone in its cluster
+    C = sp.coo_matrix(A)
+    edge = (C.row != C.col) & (C.data > 0)
+    G = sp.csr_matrix((np.ones(int(edge.sum()), dtype=np.int8), (C.row[edge], C.col[edge])), shape=(N, N))
+    n_comp, comp = csgraph.connected_components(G, directed=False)
+    assert len(np.unique(np.asarray(lab, dtype=np.int64) * n_comp + comp)) == lab.n_clusters
+    alone = (np.bincount(C.row[edge], minlength=N) + np.bincount(C.col[edge], minlength=N)) == 0
+    assert (sizes[np.asarray(lab)[alone]] == 1).all()
 
 
 def test_against_reference_outputs(golden_dir):
