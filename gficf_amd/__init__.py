@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     cluster_signatures,
     clustcells,
     clustcells_graph,
+    computePCADim,
+    csc_tmm,
     find_nn,
     HipOps,
     default_context,
@@ -27,9 +29,14 @@ from .api import (  # noqa: F401
     jaccard_expand,
     phenograph,
     p_adjust_fdr,
+    pca_dim_rule,
+    pca_project,
     rcpp_parallel_jaccard_coef,
     rcpp_parallel_WMU_test,
     rcpp_WMU_test,
+    rsvd,
+    runLSA,
+    runPCA,
     run_modularity_clustering,
     transpose_gficf,
 )

@@ -10,6 +10,7 @@ Two layers over the C ABI (include/gficf_hip.h):
     - ``gficf(M, cell_proportion_max, cell_proportion_min, storeRaw, normalize, verbose)``
                                                          reference R/gficf.R:17-33
     - ``gficf_with_weights(M, w)``                       reference R/cellClassifier.R:50-53
+    - ``runPCA`` / ``runLSA`` / ``computePCADim``        reference R/dimensinalityReduction.R:19-133,206-230 (libgficf_pca.so)
 * ``HipOps``: the device-resident pipeline stages on torch CUDA tensors (torch is only
   the owner of device memory / streams here), used by the bench and the multi-GPU path.
 
@@ -772,6 +773,185 @@ def transpose_gficf(gficf_mat, ctx: Context | None = None):
     return T
 
 
+# ------------------------------------------------------------------ PCA / LSA (libgficf_pca.so)
+RSVD_MAX_L = 128
+
+
+def csc_tmm(A_csc, X, ctx: Context | None = None) -> np.ndarray:
+    """``t(A) %*% X`` for a sparse ``A`` (nrows x ncols, scipy CSC) and a dense ``X`` (nrows x l, l <= 128): ncols x l.  The
+    building block of :func:`rsvd` and of :func:`pca_project` (``gficf_csc_tmm_host``)."""
+    from . import _pca_lib
+
+    M, colptr, rowidx, x = _csc_parts(A_csc)
+    nrows, ncols = M.shape
+    X = np.asfortranarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] != nrows:
+        raise ValueError("X must be a matrix with one row per row of A")
+    l = X.shape[1]
+    Y = np.zeros((l, ncols), dtype=np.float64)                # C-order (l, ncols) == column-major ncols x l
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_pca_lib.load().gficf_csc_tmm_host(ctx.handle, nrows, ncols, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), _np_ptr(X), l, _np_ptr(Y)))
+    return Y.T
+
+
+def rsvd(A_csc_genes_x_cells, k: int, p: int = 10, q: int = 2, seed: int = 180582, omega=None, centre: bool = False,
+         ctx: Context | None = None) -> dict:
+    """``rsvd::rsvd(t(M), k, p = 10, q = 2)`` / the decomposition inside ``rsvd::rpca`` for the genes x cells matrix ``M``
+    (scipy CSC): the randomized SVD of the cells x genes matrix ``A = t(M)``, with ``centre`` of ``A`` minus its column means
+    (never densified).  RELAXED CONTRACT (include/gficf_pca.h): the algorithm is rsvd's, its bits are not — the test matrix
+    ``omega`` (min(N, G) x l, l = min(k + p, N, G)) is drawn here, ``np.random.default_rng(seed).standard_normal``, unless given;
+    the library itself holds no generator.  Returns ``d`` (k), ``u`` (N x k), ``v`` (G x k), ``cells`` = ``u * d`` (what the
+    library computes; ``u`` is that divided by ``d``, zero where ``d`` is), ``centre`` (the gene means, or None).  Every
+    component is signed so that the entry of largest magnitude of its ``v`` column is positive."""
+    from . import _pca_lib
+
+    M, colptr, rowidx, x = _csc_parts(A_csc_genes_x_cells)
+    G, N = M.shape
+    k, n = int(k), min(G, N)
+    if omega is None:
+        l = min(k + int(p), n)
+        omega = np.random.default_rng(seed).standard_normal((n, l))
+    omega = np.asfortranarray(omega, dtype=np.float64)
+    if omega.ndim != 2 or omega.shape[0] != n:
+        raise ValueError(f"omega must have min(N, G) = {n} rows")
+    l = omega.shape[1]
+    d = np.zeros(max(k, 1), dtype=np.float64)
+    cells = np.zeros((max(k, 1), N), dtype=np.float64)        # C-order (k, N) == column-major N x k
+    genes = np.zeros((max(k, 1), G), dtype=np.float64)
+    mu = np.zeros(G, dtype=np.float64) if centre else None
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_pca_lib.load().gficf_rsvd_host(ctx.handle, G, N, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), 1 if centre else 0,
+                                          _np_ptr(omega), k, l, int(q), _np_ptr(d), _np_ptr(cells), _np_ptr(genes), _np_ptr(mu)))
+    cells, genes = cells.T, genes.T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = np.where(d > 0, cells / d, 0.0)
+    return {"d": d, "u": u, "v": genes, "cells": cells, "centre": mu}
+
+
+def _pca_dim(data: dict, dim):
+    if dim is None:
+        if data.get("dimPCA") is None:
+            raise ValueError("Specify the number of dims or run computePCADim first")
+        return int(data["dimPCA"])
+    data["dimPCA"] = int(dim)
+    return int(dim)
+
+
+def _pca_unsupported(var_scale, use_odgenes, randomized):
+    if use_odgenes or var_scale:
+        raise NotImplementedError("use_odgenes / var_scale need findOverDispersed (the mgcv::gam fit of the reference), which is not "
+                                  "provided: pass use_odgenes=False and var_scale=False")
+    if not randomized:
+        raise NotImplementedError("randomized=False is the reference's full decomposition (RSpectra::svds / prcomp), which is not "
+                                  "provided: pass randomized=True")
+
+
+def runPCA(data: dict, dim=None, var_scale: bool = False, centre: bool = False, randomized: bool = True, seed: int = 180582,
+           use_odgenes: bool = False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
+    """``runPCA(data, dim, var.scale, centre, randomized, seed, use.odgenes, n.odgenes, plot.odgenes)`` of the reference
+    (R/dimensinalityReduction.R:85-133): ``rsvd::rpca(t(data$gficf), k = dim, center = centre, scale = F)`` on the device
+    (:func:`rsvd`, relaxed contract).  ``data["pca"]`` becomes ``{"cells": N x dim (rpca's x), "genes": G x dim (its rotation),
+    "centre": centre, "rescale": var_scale}`` plus ``"mean"``, the gene means that were subtracted (None without ``centre``; the
+    reference's centring densifies and keeps nothing for later), and ``data["dimPCA"] = dim``."""
+    if use_odgenes and data.get("rawCounts") is None:
+        raise ValueError("Raw Counts absent! Please run gficf normalization with storeRaw = T")
+    dim = _pca_dim(data, dim)
+    _pca_unsupported(var_scale, use_odgenes, randomized)
+    r = rsvd(data["gficf"], dim, seed=seed, centre=bool(centre), ctx=ctx)
+    data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": bool(centre), "rescale": bool(var_scale), "mean": r["centre"]}
+    return data
+
+
+def runLSA(data: dict, dim=None, var_scale: bool = False, centre: bool = False, randomized: bool = True, seed: int = 180582,
+           use_odgenes: bool = False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
+    """``runLSA(...)`` of the reference (R/dimensinalityReduction.R:19-65): ``rsvd::rsvd(t(data$gficf), k = dim)``, then
+    ``cells = u %*% diag(d)`` and ``genes = v``.  As in the reference ``centre`` is accepted and not used
+    (``data$pca$centre <- F``, :59)."""
+    if use_odgenes and data.get("rawCounts") is None:
+        raise ValueError("Raw Counts absent! Please run gficf normalization with storeRaw = T")
+    dim = _pca_dim(data, dim)
+    _pca_unsupported(var_scale, use_odgenes, randomized)
+    r = rsvd(data["gficf"], dim, seed=seed, centre=False, ctx=ctx)
+    data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": False, "rescale": bool(var_scale), "mean": None}
+    return data
+
+
+def pca_dim_rule(d):
+    """The elbow rule of ``computePCADim`` (reference R/dimensinalityReduction.R:219-225), literally: the shares
+    ``d^2 / sum(d^2)`` over the values computed, their successive differences relative to the first one, the 1-based positions
+    ``w`` where that ratio is below 0.1, and ``w[ix]`` for the first ``ix`` at which ``cumsum(diff(w) == 1)`` exceeds 1.
+    Returns None where R would give NA."""
+    d = np.asarray(d, dtype=np.float64)
+    ev = d ** 2 / np.sum(d ** 2)
+    df = np.diff(ev)
+    if len(df) == 0:
+        return None
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = df / df[0]
+    w = np.flatnonzero(ratio < 0.1) + 1
+    hit = np.flatnonzero(np.cumsum(np.diff(w) == 1) > 1)
+    return int(w[hit[0]]) if len(hit) else None
+
+
+def computePCADim(data: dict, randomized: bool = True, subsampling: bool = False, plot: bool = False, seed: int = 180582,
+                  ctx: Context | None = None) -> dict:
+    """``computePCADim(data, randomized, subsampling, plot)`` of the reference (R/dimensinalityReduction.R:206-230):
+    ``rsvd(t(data$gficf), k = min(50, N))`` and the elbow rule (:func:`pca_dim_rule`) on its ``d``; ``data["dimPCA"]`` is set
+    and the reference's line printed.  ``subsampling``: 5 % of the cells, drawn with numpy's generator from ``seed`` (the
+    reference uses R's ``sample``).  Raises where the reference would store NA."""
+    if not randomized:
+        raise NotImplementedError("randomized=False is RSpectra::svds, which is not provided: pass randomized=True")
+    M = data["gficf"]
+    N = M.shape[1]
+    if subsampling:
+        pick = np.random.default_rng(seed).choice(N, size=int(round(N / 100 * 5)), replace=False)
+        M = M[:, pick]
+    d = rsvd(M, min(50, M.shape[1]), seed=seed, ctx=ctx)["d"]
+    if plot:
+        try:
+            import matplotlib.pyplot as plt
+
+            plt.plot(np.arange(1, len(d) + 1), d ** 2 / np.sum(d ** 2), "o")
+            plt.xlabel("components")
+            plt.ylabel("explained.var")
+        except ImportError:
+            warnings.warn("computePCADim: plot=True needs matplotlib, which is not installed", stacklevel=2)
+    dim = pca_dim_rule(d)
+    if dim is None:
+        raise ValueError("computePCADim: the elbow rule selects no dimension (the reference would store NA)")
+    print("Number of estimated dimensions =", dim)
+    data["dimPCA"] = dim
+    return data
+
+
+def pca_project(data: dict, gficf_new, ctx: Context | None = None) -> np.ndarray:
+    """``x %*% data$pca$genes`` of ``embedNewCells`` (reference R/cellClassifier.R:54-64) for ``gficf_new``, the genes x
+    new-cells GF-ICF matrix of :func:`gficf_with_weights` over the genes of ``data["pca"]["genes"]``: the new cells in the PCA
+    space, n_new x dim.  After ``runPCA(centre=True)`` the training gene means are subtracted first (the reference's
+    ``scaleMatrix`` is a stub that does nothing)."""
+    from . import _pca_lib
+
+    if data.get("pca") is None:
+        raise ValueError("First run runPCA or runLSA to reduce dimensionality")
+    genes = np.asfortranarray(data["pca"]["genes"], dtype=np.float64)
+    M, colptr, rowidx, x = _csc_parts(gficf_new)
+    G, n_new = M.shape
+    if genes.ndim != 2 or genes.shape[0] != G:
+        raise ValueError("gficf_new must have one row per row of data['pca']['genes']")
+    k = genes.shape[1]
+    mu = None
+    if data["pca"].get("centre"):
+        mu = np.ascontiguousarray(data["pca"]["mean"], dtype=np.float64)
+    out = np.zeros((k, n_new), dtype=np.float64)              # C-order (k, n_new) == column-major n_new x k
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_pca_lib.load().gficf_pca_project_host(ctx.handle, G, n_new, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), _np_ptr(genes), k,
+                                                 _np_ptr(mu), _np_ptr(out)))
+    return out.T
+
+
 # ------------------------------------------------------------------ kNN, reference-shaped
 def find_nn(X, k: int, include_self: bool = True, metric: str = "manhattan", ctx: Context | None = None) -> dict:
     """The neighbour search in front of the Jaccard build, shaped like the reference's call
@@ -1250,6 +1430,55 @@ class HipOps:
         from . import _markers_lib
 
         check(_markers_lib.load().gficf_cluster_markers_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
+        """Device scratch of ``rsvd`` (libgficf_pca.so)."""
+        from . import _pca_lib
+
+        return int(_pca_lib.load().gficf_rsvd_workspace_bytes(int(G), int(N), int(nnz), int(l)))
+
+    def rsvd(self, G, n_cells, colptr, rowidx, x, centre, omega, k, l, q, ws, d, cells, genes, mean=None):
+        """Randomized SVD on device-resident tensors (colptr int64, rowidx int32, x float64: the genes x cells CSC matrix;
+        omega: (l, min(N, G)) float64 == column-major min(N, G) x l; ws uint8 of ``rsvd_workspace_bytes``); d: k, cells: (k, N),
+        genes: (k, G), mean: G (with ``centre``) float64.  Enqueues only: call ``rsvd_sync(ws)`` to wait and to collect the
+        deferred input errors."""
+        from . import _pca_lib
+
+        check(_pca_lib.load().gficf_rsvd_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x), int(rowidx.numel()),
+                                                1 if centre else 0, _tptr(omega), int(k), int(l), int(q), _tptr(ws),
+                                                int(ws.numel() * ws.element_size()), _tptr(d), _tptr(cells), _tptr(genes), _tptr(mean)))
+
+    def rsvd_sync(self, ws):
+        from . import _pca_lib
+
+        check(_pca_lib.load().gficf_rsvd_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def csc_tmm_workspace_bytes(nrows: int, ncols: int, nnz: int, l: int) -> int:
+        from . import _pca_lib
+
+        return int(_pca_lib.load().gficf_csc_tmm_workspace_bytes(int(nrows), int(ncols), int(nnz), int(l)))
+
+    def csc_tmm(self, nrows, ncols, colptr, rowidx, x, X, l, ws, Y):
+        """``Y = t(A) X`` for the nrows x ncols CSC matrix A; X: (l, nrows), Y: (l, ncols) float64 == column-major nrows x l and
+        ncols x l.  Enqueues only (``rsvd_sync(ws)`` collects the deferred errors)."""
+        from . import _pca_lib
+
+        check(_pca_lib.load().gficf_csc_tmm_device(self._bind(), int(nrows), int(ncols), _tptr(colptr), _tptr(rowidx), _tptr(x),
+                                                   int(rowidx.numel()), _tptr(X), int(l), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(Y)))
+
+    @staticmethod
+    def orthonormalize_workspace_bytes(m: int, l: int) -> int:
+        from . import _pca_lib
+
+        return int(_pca_lib.load().gficf_orthonormalize_workspace_bytes(int(m), int(l)))
+
+    def orthonormalize(self, m, l, Y, ws):
+        """``orth`` in place on Y: (l, m) float64 == column-major m x l (include/gficf_pca.h).  Enqueues only."""
+        from . import _pca_lib
+
+        check(_pca_lib.load().gficf_orthonormalize_device(self._bind(), int(m), int(l), _tptr(Y), _tptr(ws), int(ws.numel() * ws.element_size())))
 
     def louvain_workspace_bytes(self, N: int, nnz: int, n_start: int = 1) -> int:
         """Device scratch of ``louvain``: with ``n_start`` given, enough for min(n_start, 16) starts to run together (one launch set)."""
