@@ -15,7 +15,9 @@ from .api import (  # noqa: F401
     clustcells_graph,
     computePCADim,
     csc_tmm,
+    find_ab_params,
     find_nn,
+    fuzzy_simplicial_set,
     HipOps,
     default_context,
     device_count,
@@ -37,8 +39,12 @@ from .api import (  # noqa: F401
     rsvd,
     runLSA,
     runPCA,
+    runReduction,
     run_modularity_clustering,
     transpose_gficf,
+    umap,
+    umap_init,
+    umap_layout,
 )
 
 __version__ = "0.2.0"

@@ -11,6 +11,7 @@ Two layers over the C ABI (include/gficf_hip.h):
                                                          reference R/gficf.R:17-33
     - ``gficf_with_weights(M, w)``                       reference R/cellClassifier.R:50-53
     - ``runPCA`` / ``runLSA`` / ``computePCADim``        reference R/dimensinalityReduction.R:19-133,206-230 (libgficf_pca.so)
+    - ``runReduction(data, reduction, ...)``             reference R/dimensinalityReduction.R:157-192 (libgficf_umap.so)
 * ``HipOps``: the device-resident pipeline stages on torch CUDA tensors (torch is only
   the owner of device memory / streams here), used by the bench and the multi-GPU path.
 
@@ -952,6 +953,222 @@ def pca_project(data: dict, gficf_new, ctx: Context | None = None) -> np.ndarray
     return out.T
 
 
+# ------------------------------------------------------------------ embedding (libgficf_umap.so)
+REDUCTIONS = ("tumap", "umap")
+_REDUCTION_KW = {"n_neighbors": 15, "metric": "euclidean", "n_epochs": None, "learning_rate": 1.0, "min_dist": 0.01, "spread": 1.0, "a": None,
+                 "b": None, "negative_sample_rate": 5, "repulsion_strength": 1.0, "set_op_mix_ratio": 1.0, "local_connectivity": 1.0,
+                 "init": "pca"}
+_umap_ops: dict = {}
+
+
+def _umap_hip(device: int = 0) -> "HipOps":
+    """The device-resident stages behind the host-data building blocks (torch owns their device memory)."""
+    if device not in _umap_ops:
+        _umap_ops[device] = HipOps(device)
+    return _umap_ops[device]
+
+
+def find_ab_params(spread: float = 1.0, min_dist: float = 0.01):
+    """The curve parameters ``a``, ``b`` of UMAP for ``spread`` and ``min_dist``, fitted on the host as umap-learn's
+    ``find_ab_params`` does: least squares (``scipy.optimize.curve_fit``) of ``1 / (1 + a x^(2b))`` to the curve that is 1 for
+    ``x < min_dist`` and ``exp(-(x - min_dist) / spread)`` beyond, on ``linspace(0, 3 spread, 300)``."""
+    from scipy.optimize import curve_fit
+
+    spread, min_dist = float(spread), float(min_dist)
+    if not spread > 0 or not min_dist >= 0:
+        raise ValueError("spread must be positive and min_dist non-negative")
+    xv = np.linspace(0.0, 3.0 * spread, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    (a, b), _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2.0 * b)), xv, yv)
+    return float(a), float(b)
+
+
+def umap_init(init, pca_cells, N: int, seed: int) -> np.ndarray:
+    """The initial coordinates of :func:`runReduction`, N x 2 float64.  ``"pca"``: the first two columns of ``pca_cells`` scaled
+    to a largest magnitude of 10, plus normal noise of standard deviation 1e-4 from ``default_rng(seed)``; ``"random"``: uniform
+    on [-10, 10) from the same generator; an N x 2 array is taken as it is.  ``"spectral"`` (uwot's default) is not provided."""
+    if isinstance(init, str):
+        if init == "spectral":
+            raise NotImplementedError("init='spectral' (uwot's default) is not provided: pass init='pca' (the default here), "
+                                      "'random' or an N x 2 array")
+        if init not in ("pca", "random"):
+            raise ValueError("init must be 'pca', 'random' or an N x 2 array")
+        rng = np.random.default_rng(seed)
+        if init == "random":
+            return rng.uniform(-10.0, 10.0, size=(N, 2))
+        if pca_cells is None or np.ndim(pca_cells) != 2 or np.shape(pca_cells)[1] < 2:
+            raise ValueError("init='pca' needs at least two PCA components")
+        Y = np.array(np.asarray(pca_cells)[:, :2], dtype=np.float64)
+        top = np.abs(Y).max()
+        if top > 0:
+            Y *= 10.0 / top
+        return Y + rng.normal(0.0, 1e-4, size=(N, 2))
+    Y = np.array(init, dtype=np.float64)
+    if Y.shape != (N, 2):
+        raise ValueError(f"init must be 'pca', 'random' or an N x 2 = {N} x 2 array")
+    return Y
+
+
+def fuzzy_simplicial_set(idx, dist, set_op_mix_ratio: float = 1.0, local_connectivity: float = 1.0, ret_memberships: bool = False,
+                         device: int = 0):
+    """UMAP's fuzzy graph from a neighbour table as :func:`find_nn` returns it (``idx`` N x k, 1-based, column 0 the nearest
+    point; ``dist`` alike): the smoothed memberships and their symmetrisation (``gficf_umap_graph_device``, include/gficf_umap.h).
+    Returns ``(P, sigma, rho)``: the N x N scipy CSR matrix (float32, columns ascending, ``P == P.T`` bit for bit) and the two
+    float32 vectors; with ``ret_memberships`` also ``W``, the N x k float32 memberships before the symmetrisation."""
+    import scipy.sparse as sp
+
+    idx, dist = np.asarray(idx), np.asarray(dist)
+    if idx.ndim != 2 or idx.shape != dist.shape:
+        raise ValueError("idx and dist must be N x k matrices of the same shape")
+    N, k = idx.shape
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    d_idx = tc.from_numpy(np.ascontiguousarray(idx.T, dtype=np.int32)).to(dev)         # (k, N) C-order == column-major N x k
+    d_dist = tc.from_numpy(np.ascontiguousarray(dist.T, dtype=np.float32)).to(dev)
+    cap = 2 * N * k
+    ws = tc.empty(max(ops.umap_graph_workspace_bytes(N, k), 1), dtype=tc.uint8, device=dev)
+    rowptr = tc.empty(N + 1, dtype=tc.int64, device=dev)
+    col = tc.empty(max(cap, 1), dtype=tc.int32, device=dev)
+    val = tc.empty(max(cap, 1), dtype=tc.float32, device=dev)
+    nnz = tc.zeros(1, dtype=tc.int64, device=dev)
+    sigma = tc.empty(max(N, 1), dtype=tc.float32, device=dev)
+    rho = tc.empty(max(N, 1), dtype=tc.float32, device=dev)
+    w = tc.empty((max(k, 1), max(N, 1)), dtype=tc.float32, device=dev) if ret_memberships else None
+    ops.umap_graph(d_idx, d_dist, N, k, ws, rowptr, col, val, nnz, set_op_mix_ratio, local_connectivity, sigma, rho, w)
+    ops.umap_sync(ws)
+    n = int(nnz.item())
+    P = sp.csr_matrix((val[:n].cpu().numpy(), col[:n].cpu().numpy(), rowptr.cpu().numpy()), shape=(N, N))
+    if ret_memberships:
+        return P, sigma.cpu().numpy(), rho.cpu().numpy(), np.ascontiguousarray(w.cpu().numpy().T)
+    return P, sigma.cpu().numpy(), rho.cpu().numpy()
+
+
+def umap_layout(P, init, n_epochs: int, a: float = 1.0, b: float = 1.0, learning_rate: float = 1.0, negative_sample_rate: int = 5,
+                repulsion_strength: float = 1.0, seed: int = 0, epoch_begin: int = 0, epoch_end=None, device: int = 0) -> np.ndarray:
+    """Epochs ``[epoch_begin, epoch_end)`` of ``n_epochs`` of the UMAP layout over the symmetric graph ``P`` (scipy sparse,
+    taken as CSR with sorted columns) from the coordinates ``init`` (N x 2): ``gficf_umap_layout_device``, the integer schedule
+    and the owner-computes update of include/gficf_umap.h.  Returns the N x 2 float32 coordinates; running ``[0, a)`` and then
+    ``[a, n)`` from its result gives the bits of ``[0, n)``."""
+    import scipy.sparse as sp
+
+    P = sp.csr_matrix(P)
+    if P.shape[0] != P.shape[1]:
+        raise ValueError("P must be square")
+    if not P.has_sorted_indices:
+        P = P.sorted_indices()
+    N = P.shape[0]
+    Y = np.ascontiguousarray(init, dtype=np.float32)
+    if Y.shape != (N, 2):
+        raise ValueError(f"init must be an N x 2 = {N} x 2 array")
+    epoch_end = int(n_epochs) if epoch_end is None else int(epoch_end)
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    cap = int(P.nnz)
+    rowptr = tc.from_numpy(P.indptr.astype(np.int64)).to(dev)
+    col = tc.from_numpy(np.ascontiguousarray(P.indices, dtype=np.int32)).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
+    val = tc.from_numpy(np.ascontiguousarray(P.data, dtype=np.float32)).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
+    d_Y = tc.from_numpy(Y).to(dev)
+    ws = tc.empty(max(ops.umap_layout_workspace_bytes(N, cap), 1), dtype=tc.uint8, device=dev)
+    ops.umap_layout(N, rowptr, col, val, cap, a, b, repulsion_strength, learning_rate, negative_sample_rate, n_epochs, epoch_begin, epoch_end, seed,
+                    d_Y, ws)
+    ops.umap_sync(ws)
+    return d_Y.cpu().numpy()
+
+
+def umap(X, init, n_neighbors: int = 15, metric: str = "euclidean", n_epochs: int | None = None, learning_rate: float = 1.0, a: float = 1.0,
+         b: float = 1.0, negative_sample_rate: int = 5, repulsion_strength: float = 1.0, set_op_mix_ratio: float = 1.0,
+         local_connectivity: float = 1.0, seed: int = 18051982, ret_graph: bool = True, ret_nn: bool = True, ctx: Context | None = None) -> dict:
+    """The embedding of the rows of ``X`` (N x d, d <= 128) in one call of the C ABI (``gficf_umap_host``): exact neighbour
+    search with distances, fuzzy graph, ``n_epochs`` layout sweeps from ``init`` (N x 2), all on the device.  ``n_neighbors``
+    counts the point itself, as uwot's does.  Returns ``{"embedding": N x 2, "graph": scipy CSR, "nn": {"idx", "dist"}, "a",
+    "b", "n_neighbors", "metric", "n_epochs", "seed"}`` (``graph`` / ``nn`` are None when not asked for)."""
+    import scipy.sparse as sp
+
+    from . import _umap_lib
+
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    X = np.asfortranarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-d matrix")
+    N, d = X.shape
+    Y0 = np.asfortranarray(init, dtype=np.float64)
+    if Y0.shape != (N, 2):
+        raise ValueError(f"init must be an N x 2 = {N} x 2 array")
+    k = int(n_neighbors)
+    if n_epochs is None:
+        n_epochs = 500 if N <= 10000 else 200
+    emb = np.zeros((2, N), dtype=np.float64)                  # C-order (2, N) == column-major N x 2
+    cap = max(2 * N * max(k, 0), 1)
+    rowptr = col = val = nnz = idx = dist = None
+    if ret_graph:
+        rowptr, col, val, nnz = np.zeros(N + 1, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(1, np.int64)
+    if ret_nn:
+        idx, dist = np.zeros((max(k, 1), N), np.int32), np.zeros((max(k, 1), N), np.float32)
+    ctx = ctx or default_context()
+    check(_umap_lib.load().gficf_umap_host(ctx.handle, _np_ptr(X), N, d, max(N, 1), _lib.KNN_METRICS[metric], k, float(local_connectivity),
+                                           float(set_op_mix_ratio), float(a), float(b), float(repulsion_strength), float(learning_rate),
+                                           int(negative_sample_rate), int(n_epochs), _np_ptr(Y0), int(seed) & 0xFFFFFFFFFFFFFFFF, _np_ptr(emb),
+                                           _np_ptr(rowptr), _np_ptr(col), _np_ptr(val), _np_ptr(nnz), _np_ptr(idx), _np_ptr(dist)))
+    graph = nn = None
+    if ret_graph:
+        n = int(nnz[0])
+        graph = sp.csr_matrix((val[:n].copy(), col[:n].copy(), rowptr), shape=(N, N))
+    if ret_nn:
+        nn = {"idx": np.ascontiguousarray(idx.T), "dist": np.ascontiguousarray(dist.T, dtype=np.float64)}
+    return {"embedding": np.ascontiguousarray(emb.T), "graph": graph, "nn": nn, "a": float(a), "b": float(b), "n_neighbors": k,
+            "metric": metric, "n_epochs": int(n_epochs), "seed": int(seed)}
+
+
+def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 18051982, ret_model_pred: bool = True, verbose: bool = True,
+                 ctx: Context | None = None, **kw) -> dict:
+    """``runReduction(data, reduction, nt, seed, ret_model_pred, verbose, ...)`` of the reference
+    (R/dimensinalityReduction.R:157-192, whose default is ``uwot::tumap(data$pca$cells)``) on the device (:func:`umap`).  RELAXED
+    CONTRACT (include/gficf_umap.h): the algorithm and its objective are UMAP's, the random bits and the update order are not
+    uwot's.  Further arguments, with uwot's meaning: ``n_neighbors=15, metric="euclidean", n_epochs=None`` (500 for N <= 10 000,
+    else 200), ``learning_rate=1, min_dist=0.01, spread=1, a=None, b=None, negative_sample_rate=5, repulsion_strength=1,
+    set_op_mix_ratio=1, local_connectivity=1, init="pca"`` (:func:`umap_init`; uwot's default ``"spectral"`` is not provided:
+    the one divergence in defaults).  ``"tumap"`` is a = b = 1; ``"umap"`` fits them (:func:`find_ab_params`) unless both are given.
+
+    ``data["embedded"]`` becomes a pandas DataFrame with the columns ``X`` and ``Y`` (what ``clustcells(from_embedded=True)``
+    searches), ``data["reduction"]`` the name, and with ``ret_model_pred`` ``data["uwot"]`` the dict of :func:`umap`.  Not provided,
+    each raising ``NotImplementedError``: ``reduction="tsne"``, ``init="spectral"``, and a ``data`` without ``data["pca"]`` (the
+    reference then embeds the densified ``t(gficf)``).  ``nt`` is accepted for signature compatibility (no CPU threads)."""
+    import pandas as pd
+
+    if reduction == "tsne":
+        raise NotImplementedError("reduction='tsne' (Rtsne) is not provided: use 'tumap' or 'umap'")
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS} ('tsne' is not provided)")
+    unknown = sorted(set(kw) - set(_REDUCTION_KW))
+    if unknown:
+        raise TypeError(f"runReduction: unknown argument(s) {unknown}")
+    o = dict(_REDUCTION_KW, **kw)
+    if data.get("pca") is None:
+        raise NotImplementedError("runReduction without data['pca'] (the reference embeds the densified t(gficf)) is not provided: "
+                                  "run runPCA or runLSA first")
+    if o["metric"] not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    cells = np.asarray(data["pca"]["cells"], dtype=np.float64)
+    N = cells.shape[0]
+    Y0 = umap_init(o["init"], cells, N, seed)
+    if reduction == "tumap":
+        a = b = 1.0
+    elif o["a"] is not None and o["b"] is not None:
+        a, b = float(o["a"]), float(o["b"])
+    else:
+        a, b = find_ab_params(o["spread"], o["min_dist"])
+    tsmessage(f"Running {reduction} on {N} cells, {cells.shape[1]} components", verbose=verbose)
+    r = umap(cells, Y0, n_neighbors=o["n_neighbors"], metric=o["metric"], n_epochs=o["n_epochs"], learning_rate=o["learning_rate"], a=a, b=b,
+             negative_sample_rate=o["negative_sample_rate"], repulsion_strength=o["repulsion_strength"], set_op_mix_ratio=o["set_op_mix_ratio"],
+             local_connectivity=o["local_connectivity"], seed=seed, ret_graph=bool(ret_model_pred), ret_nn=bool(ret_model_pred), ctx=ctx)
+    data["embedded"] = pd.DataFrame(r["embedding"], columns=["X", "Y"])
+    data["reduction"] = reduction
+    if ret_model_pred:
+        data["uwot"] = r
+    return data
+
+
 # ------------------------------------------------------------------ kNN, reference-shaped
 def find_nn(X, k: int, include_self: bool = True, metric: str = "manhattan", ctx: Context | None = None) -> dict:
     """The neighbour search in front of the Jaccard build, shaped like the reference's call
@@ -1479,6 +1696,47 @@ class HipOps:
         from . import _pca_lib
 
         check(_pca_lib.load().gficf_orthonormalize_device(self._bind(), int(m), int(l), _tptr(Y), _tptr(ws), int(ws.numel() * ws.element_size())))
+
+    @staticmethod
+    def umap_graph_workspace_bytes(N: int, k: int) -> int:
+        """Device scratch of ``umap_graph`` (libgficf_umap.so)."""
+        from . import _umap_lib
+
+        return int(_umap_lib.load().gficf_umap_graph_workspace_bytes(int(N), int(k)))
+
+    def umap_graph(self, idx_cm, dist_cm, N, k, ws, rowptr, col, val, nnz, set_op_mix_ratio=1.0, local_connectivity=1.0, sigma=None, rho=None, w=None):
+        """UMAP's fuzzy graph from the search's own output (idx_cm int32 / dist_cm float32: (k, ld) == column-major N x k, as
+        ``knn_search`` writes them): rowptr int64 N + 1, col int32 / val float32 of at least 2 N k entries, nnz int64 (1), sigma /
+        rho float32 N or None, w (the memberships, (k, N) float32 == column-major N x k) or None.  Enqueues only: ``umap_sync(ws)`` waits and collects the deferred input errors."""
+        from . import _umap_lib
+
+        ld = idx_cm.shape[1] if idx_cm.dim() == 2 else N
+        check(_umap_lib.load().gficf_umap_graph_device(self._bind(), _tptr(idx_cm), _tptr(dist_cm), int(N), int(k), int(ld),
+                                                       float(local_connectivity), float(set_op_mix_ratio), _tptr(ws),
+                                                       int(ws.numel() * ws.element_size()), _tptr(rowptr), _tptr(col), _tptr(val),
+                                                       int(min(col.numel(), val.numel())), _tptr(nnz), _tptr(sigma), _tptr(rho), _tptr(w)))
+
+    @staticmethod
+    def umap_layout_workspace_bytes(N: int, capacity: int) -> int:
+        from . import _umap_lib
+
+        return int(_umap_lib.load().gficf_umap_layout_workspace_bytes(int(N), int(capacity)))
+
+    def umap_layout(self, N, rowptr, col, val, capacity, a, b, gamma, learning_rate, negative_sample_rate, n_epochs, epoch_begin, epoch_end, seed,
+                    Y, ws):
+        """Epochs [epoch_begin, epoch_end) of n_epochs of the layout, in place on Y ((N, 2) float32), over the graph of
+        ``umap_graph`` (``capacity``: the entries of col / val that may be read).  One launch per epoch; enqueues only."""
+        from . import _umap_lib
+
+        check(_umap_lib.load().gficf_umap_layout_device(self._bind(), int(N), _tptr(rowptr), _tptr(col), _tptr(val), int(capacity), float(a),
+                                                        float(b), float(gamma), float(learning_rate), int(negative_sample_rate), int(n_epochs),
+                                                        int(epoch_begin), int(epoch_end), int(seed) & 0xFFFFFFFFFFFFFFFF, _tptr(Y), _tptr(ws),
+                                                        int(ws.numel() * ws.element_size())))
+
+    def umap_sync(self, ws):
+        from . import _umap_lib
+
+        check(_umap_lib.load().gficf_umap_sync(self._bind(), _tptr(ws)))
 
     def louvain_workspace_bytes(self, N: int, nnz: int, n_start: int = 1) -> int:
         """Device scratch of ``louvain``: with ``n_start`` given, enough for min(n_start, 16) starts to run together (one launch set)."""
