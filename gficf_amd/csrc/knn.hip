@@ -476,7 +476,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void k_knn_tiles(const KnnTileArgs 
         if (nvalid < KNN_TC) epilogue(std::true_type{});
         else epilogue(std::false_type{});
         if (PRUNE) {
-          // this wave's largest k-th best (rows without a query do not count; an unfilled list is +inf)
+          // this wave's largest k-th best (rows without a query do not count; an unfilled list is +inf).  From 0, never below: cosine
+          // k-th bests can round below 0 while k_knn_lb clamps the bounds at 0 — tiles with bound 0 have to stay in reach
           float tm = 0.0f;
 #pragma unroll
           for (int r = 0; r < RQ; ++r)

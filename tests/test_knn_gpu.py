@@ -78,7 +78,8 @@ def test_pruned_search_on_unclustered_and_degenerate_data(monkeypatch):
     cases = {"uniform": rng.uniform(size=(3000, 6)), "all equal": np.ones((600, 4)), "two points repeated": np.repeat(np.array([[0.0, 0.0], [5.0, 1.0]]), 400, axis=0),
              "line": np.linspace(0, 1, 2000)[:, None] * np.ones((1, 3))}
     for name, X in cases.items():
-        for metric in ("manhattan", "euclidean"):
+        # cosine where the rows have a direction to compare: "line" is one zero row and 1999 copies of one direction (keys around and below 0)
+        for metric in ("manhattan", "euclidean") + (("cosine",) if name in ("uniform", "line") else ()):
             got = gficf_amd.find_nn(X, 17, True, metric)
             widx, wdist = oracle.knn(X, 17, metric, nthreads=8)
             assert np.array_equal(got["idx"], widx), (name, metric)
