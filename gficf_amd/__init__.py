@@ -12,14 +12,17 @@ from .api import (  # noqa: F401
     cluster_markers,
     cluster_signatures,
     clustcells,
+    classify_cells,
     clustcells_graph,
     computePCADim,
     csc_tmm,
     find_ab_params,
     find_nn,
+    find_nn_query,
     fuzzy_simplicial_set,
     HipOps,
     default_context,
+    embedNewCells,
     device_count,
     findClusterMarkers,
     gficf,
@@ -29,6 +32,7 @@ from .api import (  # noqa: F401
     jaccard_counts,
     jaccard_edges,
     jaccard_expand,
+    knn_classify,
     phenograph,
     p_adjust_fdr,
     pca_dim_rule,
@@ -45,6 +49,7 @@ from .api import (  # noqa: F401
     umap,
     umap_init,
     umap_layout,
+    umap_transform,
 )
 
 __version__ = "0.2.0"

@@ -1169,6 +1169,202 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     return data
 
 
+# ------------------------------------------------------------------ new cells (libgficf_transform.so)
+def _query_pair(X_train, Q):
+    X = np.asfortranarray(X_train, dtype=np.float64)
+    Qm = np.asfortranarray(Q, dtype=np.float64)
+    if X.ndim != 2 or Qm.ndim != 2:
+        raise ValueError("X_train and Q must be 2-d matrices")
+    if X.shape[1] != Qm.shape[1]:
+        raise ValueError(f"Q has {Qm.shape[1]} columns, X_train has {X.shape[1]}")
+    return X, Qm
+
+
+def find_nn_query(X_train, Q, k: int, metric: str = "euclidean", ctx: Context | None = None) -> dict:
+    """The ``k`` nearest rows of ``X_train`` (N x d) for every row of ``Q`` (M x d): exact, f32, the arithmetic and the tie rule
+    of :func:`find_nn` (``gficf_transform_search_host``, include/gficf_transform.h), so ``find_nn_query(X, X, k)`` is
+    ``find_nn(X, k, True)`` bit for bit.  Returns ``{"idx": M x k int32, 1-based ids of training rows, "dist": M x k float64}``."""
+    from . import _transform_lib
+
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    X, Qm = _query_pair(X_train, Q)
+    (N, d), M, k = X.shape, Qm.shape[0], int(k)
+    idx = np.zeros((max(k, 1), M), dtype=np.int32)            # C-order (k, M) == column-major M x k
+    dist = np.zeros((max(k, 1), M), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_transform_lib.load().gficf_transform_search_host(ctx.handle, _np_ptr(X), N, max(N, 1), _np_ptr(Qm), M, max(M, 1), d, k,
+                                                            _lib.KNN_METRICS[metric], _np_ptr(idx), _np_ptr(dist)))
+    return {"idx": np.ascontiguousarray(idx.T), "dist": np.ascontiguousarray(dist.T)}
+
+
+def umap_transform(Q, model: dict, X_train, n_epochs: int | None = None, learning_rate: float | None = None, negative_sample_rate: int = 5,
+                   repulsion_strength: float = 1.0, local_connectivity: float = 1.0, seed: int | None = None, init="weighted",
+                   query_offset: int = 0, epoch_begin: int = 0, epoch_end: int | None = None, ret_extra: bool = False,
+                   ctx: Context | None = None):
+    """``uwot::umap_transform`` for the rows of ``Q`` (M x d): their place in the plane of ``model``, the dict of :func:`umap`
+    as :func:`runReduction` stores it in ``data["uwot"]``, trained on ``X_train`` (N x d) — one call of the C ABI
+    (``gficf_transform_host``): search against the training rows, memberships, weighted initial positions, layout sweeps in
+    which only the new cells move.  RELAXED CONTRACT (include/gficf_transform.h).
+
+    From the model: ``embedding``, ``a``, ``b``, ``n_neighbors``, ``metric``, ``n_epochs``, ``seed``.  ``n_epochs=None`` means
+    ``max(1, round(model["n_epochs"] / 3))``; ``learning_rate=None`` means 0.25, a quarter of the training default, as
+    umap-learn's transform takes it; ``seed=None`` the model's.  The model does not record ``learning_rate``,
+    ``negative_sample_rate``, ``repulsion_strength`` or ``local_connectivity``: a caller who trained with other values passes
+    them again.  ``init``: ``"weighted"`` or an M x 2 array.  The result for row i depends on that row, the model and
+    ``query_offset + i`` only: a batch may be cut into pieces.  Returns M x 2 float64; with ``ret_extra`` a dict with
+    ``embedding``, ``idx``, ``dist``, ``w``, ``sigma``, ``rho`` and ``init`` (the positions the sweeps started from)."""
+    from . import _transform_lib
+
+    X, Qm = _query_pair(X_train, Q)
+    (N, d), M = X.shape, Qm.shape[0]
+    Yt = np.asfortranarray(model["embedding"], dtype=np.float64)
+    if Yt.shape != (N, 2):
+        raise ValueError(f"model['embedding'] must be N x 2 = {N} x 2: X_train is not what the model was trained on")
+    metric, k = model["metric"], int(model["n_neighbors"])
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    if n_epochs is None:
+        n_epochs = max(1, int(round(model["n_epochs"] / 3)))
+    epoch_end = int(n_epochs) if epoch_end is None else int(epoch_end)
+    learning_rate = 0.25 if learning_rate is None else float(learning_rate)
+    seed = int(model["seed"]) if seed is None else int(seed)
+    Y0 = None
+    if not (isinstance(init, str) and init == "weighted"):
+        if isinstance(init, str):
+            raise ValueError("init must be 'weighted' or an M x 2 array")
+        Y0 = np.asfortranarray(init, dtype=np.float64)
+        if Y0.shape != (M, 2):
+            raise ValueError(f"init must be 'weighted' or an M x 2 = {M} x 2 array")
+    emb = np.zeros((2, M), dtype=np.float64)                  # C-order (2, M) == column-major M x 2
+    idx = dist = w = sigma = rho = y0 = None
+    if ret_extra:
+        idx, dist, w = (np.zeros((max(k, 1), M), t) for t in (np.int32, np.float32, np.float32))
+        sigma, rho, y0 = np.zeros(M, np.float32), np.zeros(M, np.float32), np.zeros((2, M), np.float64)
+    ctx = ctx or default_context()
+    check(_transform_lib.load().gficf_transform_host(
+        ctx.handle, _np_ptr(X), N, max(N, 1), _np_ptr(Yt), _np_ptr(Qm), M, max(M, 1), d, _lib.KNN_METRICS[metric], k, float(local_connectivity),
+        float(model["a"]), float(model["b"]), float(repulsion_strength), learning_rate, int(negative_sample_rate), int(n_epochs),
+        int(epoch_begin), epoch_end, _np_ptr(Y0), seed & 0xFFFFFFFFFFFFFFFF, int(query_offset), _np_ptr(emb), _np_ptr(idx), _np_ptr(dist),
+        _np_ptr(w), _np_ptr(sigma), _np_ptr(rho), _np_ptr(y0)))
+    emb = np.ascontiguousarray(emb.T)
+    if not ret_extra:
+        return emb
+    return {"embedding": emb, "idx": np.ascontiguousarray(idx.T), "dist": np.ascontiguousarray(dist.T), "w": np.ascontiguousarray(w.T),
+            "sigma": sigma, "rho": rho, "init": np.ascontiguousarray(y0.T)}
+
+
+def knn_classify(train, test, classes, k: int = 7, metric: str = "euclidean", ctx: Context | None = None) -> np.ndarray:
+    """``class::knn(train, test, cl, k)``: for every row of ``test`` the class with the most votes among its ``k`` nearest rows of
+    ``train`` (``gficf_transform_classify_host``).  Exact search; among classes that tie, the one whose first member is the
+    nearer neighbour wins (``class::knn`` breaks ties at random and widens k to the points tied at the k-th distance: neither
+    is reproduced).  ``classes``: one label per row of ``train``; the predictions have its dtype."""
+    from . import _transform_lib
+
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    X, Qm = _query_pair(train, test)
+    (N, d), M = X.shape, Qm.shape[0]
+    classes = np.asarray(classes)
+    if classes.shape != (N,):
+        raise ValueError(f"classes must hold one label per row of train: {N}")
+    levels, codes = np.unique(classes, return_inverse=True)
+    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    pred = np.zeros(M, dtype=np.int32)
+    ctx = ctx or default_context()
+    check(_transform_lib.load().gficf_transform_classify_host(ctx.handle, _np_ptr(X), N, max(N, 1), _np_ptr(Qm), M, max(M, 1), d, int(k),
+                                                              _lib.KNN_METRICS[metric], _np_ptr(codes), max(len(levels), 1), _np_ptr(pred)))
+    return levels[pred]
+
+
+_TRANSFORM_KW = ("n_epochs", "learning_rate", "negative_sample_rate", "repulsion_strength", "local_connectivity", "init", "query_offset",
+                 "epoch_begin", "epoch_end")
+
+
+def _append_predicted(embedded, new_xy):
+    """The bookkeeping of embedNewCells (reference R/cellClassifier.R:83-93): trained rows NO, new rows YES, other columns NaN."""
+    import pandas as pd
+
+    emb = pd.DataFrame(embedded).copy()
+    if "predicted" not in emb.columns:
+        emb["predicted"] = "NO"
+    df = pd.DataFrame(np.asarray(new_xy, dtype=np.float64), columns=["X", "Y"])
+    for col in emb.columns[2:]:
+        df[col] = np.nan
+    df["predicted"] = "YES"
+    out = pd.concat([emb.astype({"predicted": object}), df[list(emb.columns)]], ignore_index=True)
+    out["predicted"] = pd.Categorical(out["predicted"].astype(str), categories=["NO", "YES"])
+    return out
+
+
+def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: bool = True, genes=None, ctx: Context | None = None, **kw) -> dict:
+    """``embedNewCells(data, x, nt, seed, verbose, ...)`` of the reference (R/cellClassifier.R:48-95) on the device: the new
+    cells are GF-ICF normalised with the trained ICF weights (:func:`gficf_with_weights`), projected into the trained PCA / LSA
+    space (:func:`pca_project`) and placed into the trained plane (:func:`umap_transform`, which ``**kw`` goes to: ``n_epochs,
+    learning_rate, negative_sample_rate, repulsion_strength, local_connectivity, init, query_offset, epoch_begin, epoch_end``).
+
+    ``x``: genes x new-cells sparse count matrix whose rows are those of the matrix :func:`gficf` was given (``data["genes"]``
+    selects the kept ones, standing in for the reference's match by row name), or pass ``genes``: the row of ``x`` for every
+    kept gene.  ``data["embedded"]`` gets the column ``predicted`` (categorical, levels NO and YES): NO for the trained rows, YES
+    for the appended new ones, whose other columns are NaN; ``data["pca"]["pred"]`` holds the new cells in PCA space.  Needs
+    ``data["uwot"]`` (``runReduction(ret_model_pred=True)``); ``data["reduction"] == "tsne"`` is not provided.  ``nt`` is accepted
+    for signature compatibility; ``seed`` is the reference's argument, which only its t-SNE branch uses: the sweeps take the
+    model's seed."""
+    import scipy.sparse as sp
+
+    if data.get("reduction") == "tsne":
+        raise NotImplementedError("embedNewCells after reduction='tsne' (the reference re-runs Rtsne) is not provided")
+    if data.get("uwot") is None:
+        raise ValueError("embedNewCells needs the trained model: run runReduction(ret_model_pred=True) first")
+    unknown = sorted(set(kw) - set(_TRANSFORM_KW))
+    if unknown:
+        raise TypeError(f"embedNewCells: unknown argument(s) {unknown}")
+    if data.get("pca") is None:
+        raise ValueError("First run runPCA or runLSA to reduce dimensionality")
+    rows = np.asarray(data["genes"] if genes is None else genes, dtype=np.int64)
+    if rows.shape != (len(data["w"]),):
+        raise ValueError("genes must name one row of x for every kept gene (len(data['w']))")
+    x = sp.csc_matrix(x)
+    if len(rows) and (rows.min() < 0 or rows.max() >= x.shape[0]):
+        raise ValueError(f"x has {x.shape[0]} rows: the kept genes name rows up to {int(rows.max())}")
+    tsmessage(f"Embedding {x.shape[1]} new cells", verbose=verbose)
+    sub = x[rows, :]
+    g, kept = gficf_with_weights(sub, data["w"], ctx)
+    # the rows gficf_with_weights dropped as empty come back (as empty rows): pca_project needs one per row of data["pca"]["genes"]
+    g = sp.csc_matrix((g.data, kept[g.indices].astype(np.int32), g.indptr), shape=(len(rows), x.shape[1]))
+    pred = pca_project(data, g, ctx)
+    xy = umap_transform(pred, data["uwot"], data["pca"]["cells"], ctx=ctx, **kw)
+    data["embedded"] = _append_predicted(data["embedded"], xy)
+    data["pca"]["pred"] = pred
+    return data
+
+
+CLASSIFY_METHODS = ("PCA", "embedded")
+
+
+def classify_cells(data: dict, classes, k: int = 7, seed: int = 18051982, method: str = "PCA", ctx: Context | None = None):
+    """``classify.cells(data, classes, k, seed, method)`` of the reference (R/cellClassifier.R:15-29): the new cells of
+    :func:`embedNewCells` labelled by :func:`knn_classify` from the trained ones, whose labels ``classes`` are.  ``"PCA"`` searches
+    ``data["pca"]["cells"]`` against ``data["pca"]["pred"]``; ``"embedded"`` the NO rows of the plane against the YES rows.
+    Returns a DataFrame ``cell.id`` (the new cells' row labels in ``data["embedded"]``), ``pred``.  ``seed`` is accepted for
+    the signature: nothing is random here."""
+    import pandas as pd
+
+    if method not in CLASSIFY_METHODS:
+        raise ValueError(f"method must be one of {CLASSIFY_METHODS}")
+    emb = data.get("embedded")
+    if emb is None or "predicted" not in getattr(emb, "columns", ()):
+        raise ValueError("Please embed first new cells!")
+    new = np.asarray(emb["predicted"].astype(str) == "YES")
+    if method == "PCA":
+        train, test = data["pca"]["cells"], data["pca"]["pred"]
+    else:
+        xy = np.asarray(emb[["X", "Y"]], dtype=np.float64)
+        train, test = xy[~new], xy[new]
+    pred = knn_classify(train, test, np.asarray(classes).astype(str), k, "euclidean", ctx)
+    return pd.DataFrame({"cell.id": list(emb.index[new]), "pred": pred})
+
+
 # ------------------------------------------------------------------ kNN, reference-shaped
 def find_nn(X, k: int, include_self: bool = True, metric: str = "manhattan", ctx: Context | None = None) -> dict:
     """The neighbour search in front of the Jaccard build, shaped like the reference's call
@@ -1737,6 +1933,74 @@ class HipOps:
         from . import _umap_lib
 
         check(_umap_lib.load().gficf_umap_sync(self._bind(), _tptr(ws)))
+
+    # -- new cells (libgficf_transform.so); every *_workspace_bytes scratch begins with the status word transform_sync reads
+    @staticmethod
+    def transform_workspace_bytes(stage: str, M: int, N: int = 0, k: int = 1) -> int:
+        """Device scratch of ``transform_<stage>``: stage is search (needs N), weights, init, layout or vote."""
+        from . import _transform_lib
+
+        L = _transform_lib.load()
+        if stage == "search":
+            return int(L.gficf_transform_search_workspace_bytes(int(M), int(N), int(k)))
+        return int(getattr(L, f"gficf_transform_{stage}_workspace_bytes")(int(M), int(k)))
+
+    def transform_search_split(self, M: int, N: int) -> int:
+        """The slices the candidate range is cut into for M queries against N training rows."""
+        from . import _transform_lib
+
+        return int(_transform_lib.load().gficf_transform_search_split(self.ctx.handle, int(M), int(N)))
+
+    def transform_search(self, train, N, query, M, d, k, metric, ws, idx_cm, dist_cm=None):
+        """train (N, dpad) / query (M, dpad) float32 as ``knn_prepare`` writes them; idx_cm int32 / dist_cm float32 (or None):
+        (k, ld) == column-major M x k, 1-based training ids.  Enqueues only, like every transform_* stage."""
+        from . import _transform_lib
+
+        ld = idx_cm.shape[1] if idx_cm.dim() == 2 else M
+        check(_transform_lib.load().gficf_transform_search_device(self._bind(), _tptr(train), int(N), _tptr(query), int(M), int(d), int(k),
+                                                                  _lib.KNN_METRICS[metric], _tptr(ws), int(ws.numel() * ws.element_size()),
+                                                                  _tptr(idx_cm), _tptr(dist_cm), int(ld)))
+
+    def transform_weights(self, idx_cm, dist_cm, N, M, k, ws, w_cm, local_connectivity=1.0, sigma=None, rho=None):
+        """The memberships of the search's table: w_cm (k, ld_w) float32 == column-major M x k; sigma / rho float32 M or None."""
+        from . import _transform_lib
+
+        check(_transform_lib.load().gficf_transform_weights_device(self._bind(), _tptr(idx_cm), _tptr(dist_cm), int(N), int(M), int(k),
+                                                                   int(idx_cm.shape[1]), float(local_connectivity), _tptr(ws),
+                                                                   int(ws.numel() * ws.element_size()), _tptr(w_cm), int(w_cm.shape[1]),
+                                                                   _tptr(sigma), _tptr(rho)))
+
+    def transform_init(self, idx_cm, w_cm, Y_train, N, M, k, ws, Y):
+        """Y ((M, 2) float32) = the membership-weighted mean of the k heads' positions in Y_train ((N, 2) float32)."""
+        from . import _transform_lib
+
+        check(_transform_lib.load().gficf_transform_init_device(self._bind(), _tptr(idx_cm), int(idx_cm.shape[1]), _tptr(w_cm), int(w_cm.shape[1]),
+                                                                _tptr(Y_train), int(N), int(M), int(k), _tptr(ws),
+                                                                int(ws.numel() * ws.element_size()), _tptr(Y)))
+
+    def transform_layout(self, idx_cm, w_cm, Y_train, N, M, k, a, b, gamma, learning_rate, negative_sample_rate, n_epochs, epoch_begin, epoch_end,
+                         seed, query_offset, Y, ws):
+        """Epochs [epoch_begin, epoch_end) of n_epochs in place on Y ((M, 2) float32); Y_train is read only.  One launch."""
+        from . import _transform_lib
+
+        check(_transform_lib.load().gficf_transform_layout_device(self._bind(), _tptr(idx_cm), int(idx_cm.shape[1]), _tptr(w_cm),
+                                                                  int(w_cm.shape[1]), _tptr(Y_train), int(N), int(M), int(k), float(a), float(b),
+                                                                  float(gamma), float(learning_rate), int(negative_sample_rate), int(n_epochs),
+                                                                  int(epoch_begin), int(epoch_end), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                                  int(query_offset), _tptr(Y), _tptr(ws), int(ws.numel() * ws.element_size())))
+
+    def transform_vote(self, idx_cm, labels, N, M, k, C, ws, pred, votes=None):
+        """pred (M int32) = the majority label among labels[idx - 1] (int32 N, in [0, C)); votes: (M, C) int32 or None."""
+        from . import _transform_lib
+
+        check(_transform_lib.load().gficf_transform_vote_device(self._bind(), _tptr(idx_cm), int(idx_cm.shape[1]), _tptr(labels), int(N), int(M),
+                                                                int(k), int(C), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(pred),
+                                                                _tptr(votes)))
+
+    def transform_sync(self, ws):
+        from . import _transform_lib
+
+        check(_transform_lib.load().gficf_transform_sync(self._bind(), _tptr(ws)))
 
     def louvain_workspace_bytes(self, N: int, nnz: int, n_start: int = 1) -> int:
         """Device scratch of ``louvain``: with ``n_start`` given, enough for min(n_start, 16) starts to run together (one launch set)."""
