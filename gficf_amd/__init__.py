@@ -24,9 +24,12 @@ from .api import (  # noqa: F401
     default_context,
     embedNewCells,
     device_count,
+    fgsea,
     findClusterMarkers,
     gficf,
     gficf_with_weights,
+    gmt_pathways,
+    gsea,
     jaccard_adjacency,
     jaccard_coeff,
     jaccard_counts,
@@ -41,6 +44,7 @@ from .api import (  # noqa: F401
     rcpp_parallel_WMU_test,
     rcpp_WMU_test,
     rsvd,
+    runGSEA,
     runLSA,
     runPCA,
     runReduction,

@@ -694,6 +694,174 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     return data
 
 
+# ------------------------------------------------------------------ pathways (libgficf_gsea.so)
+def gmt_pathways(gmt_file, convertToEns: bool = False, convertHu2Mm: bool = False, verbose: bool = True, gene_map=None) -> dict:
+    """``gmtPathways(gmt.file, convertToEns, convertHu2Mm, verbose)`` of the reference (R/pathwayAnalisys.R:2-42): every line of
+    the gmt file split on tabs, field 1 the name, field 2 dropped, the rest the members; pathways left without a member are
+    dropped.  Returns ``{name: [members]}`` in file order (of a repeated name the first line is kept).
+
+    The reference converts the symbols through biomaRt, which needs the network.  Here, with either flag true, ``gene_map`` (a
+    dict from symbol to a list of ids, or to one id) does that mapping: a pathway becomes the ids of its members, unique with
+    order kept, unmapped members and missing ids dropped.  A flag without ``gene_map`` raises ``NotImplementedError``.
+    """
+    if (convertToEns or convertHu2Mm) and gene_map is None:
+        raise NotImplementedError("convertToEns / convertHu2Mm look the genes up through biomaRt, which is not provided: pass "
+                                  "gene_map={symbol: [ids]}")
+    pathways = {}
+    with open(gmt_file) as f:
+        for line in f:
+            fields = line.rstrip("\r\n").split("\t")
+            while fields and fields[-1] == "":                # strsplit drops the trailing empty field
+                fields.pop()
+            if fields and fields[0] not in pathways:
+                pathways[fields[0]] = fields[2:]
+    if convertToEns or convertHu2Mm:
+        what = ("human symbols to mouse ensamble id" if convertToEns else "human symbols to mouse symbols") if convertHu2Mm \
+            else "human symbols to human ensamble id"
+        tsmessage(f".. Start converting {what}", verbose=verbose)
+        for name, members in pathways.items():
+            ids = []
+            for sym in members:
+                hit = gene_map.get(sym, [])
+                ids.extend([hit] if isinstance(hit, str) else hit)
+            pathways[name] = list(dict.fromkeys(i for i in ids if i is not None and i == i))
+        tsmessage("Done!", verbose=verbose)
+    return {name: members for name, members in pathways.items() if len(members) > 0}
+
+
+def gsea(stats, pathways_ptr, pathways_rows, nsim: int = 1000, min_size=1, max_size=np.inf, seed: int = 180582, ret_null: bool = False,
+         ctx: Context | None = None) -> dict:
+    """Gene-set enrichment of every column of ``stats`` (G x C, one ranking statistic per gene and cluster) for P pathways in
+    CSR form (``pathways_ptr``: P + 1 offsets, ``pathways_rows``: rows of ``stats``), fgsea at ``gseaParam = 0`` under the
+    relaxed contract of include/gficf_gsea.h: ES and NES are fgsea's, the p-value is ``fgseaSimple``'s estimator over ``nsim``
+    permutations (never below ``1 / (nsim + 1)``), one null per set size shared by all clusters.
+
+    Returns ``es``, ``nes``, ``pval`` (P x C; zeros where a pathway is not tested), ``size`` (P), ``tested`` (P; size within
+    ``[min_size, min(max_size, G - 1)]``) and, with ``ret_null``, ``sizes`` (the D distinct tested sizes) and ``null`` (D x nsim).
+    """
+    from . import _gsea_lib
+
+    S = np.asarray(stats, dtype=np.float64)
+    if S.ndim == 1:
+        S = S[:, None]
+    if S.ndim != 2 or S.shape[0] < 1 or S.shape[1] < 1:
+        raise ValueError("stats must be a G x C matrix")
+    G, C = S.shape
+    S = np.ascontiguousarray(S.T)                            # C-order (C, G) == column-major G x C
+    ptr = np.ascontiguousarray(pathways_ptr, dtype=np.int64)
+    rows = np.ascontiguousarray(pathways_rows, dtype=np.int32)
+    if ptr.ndim != 1 or len(ptr) < 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or rows.ndim != 1 or ptr[-1] != len(rows):
+        raise ValueError("pathways_ptr must hold P + 1 non-decreasing offsets from 0 to len(pathways_rows)")
+    if int(nsim) < 1:
+        raise ValueError("nsim must be at least 1")
+    P, nsim = len(ptr) - 1, int(nsim)
+    size = np.diff(ptr)
+    lo, hi = int(max(min_size, 1)), int(min(max_size, G - 1))
+    tested = (size >= lo) & (size <= hi)
+    sizes = np.unique(size[tested])
+    es, nes, pval = (np.zeros((C, P), dtype=np.float64) for _ in range(3))
+    null = np.zeros((len(sizes), nsim), dtype=np.float64) if ret_null else None
+    ctx = ctx or default_context()
+    check(_gsea_lib.load().gficf_gsea_host(ctx.handle, G, C, _np_ptr(S), P, _np_ptr(ptr), _np_ptr(rows), nsim, int(seed) & 0xFFFFFFFF, lo, hi,
+                                           _np_ptr(es), _np_ptr(nes), _np_ptr(pval), _np_ptr(null) if ret_null else None, len(sizes)))
+    out = {"es": es.T, "nes": nes.T, "pval": pval.T, "size": size, "tested": tested}
+    if ret_null:
+        out["sizes"], out["null"] = sizes, null
+    return out
+
+
+def _pathway_csr(pathways: dict, gene_names):
+    """The members of every pathway matched to the rows named ``gene_names`` (fgsea's ``fmatch``: the first row of a name),
+    unmatched ones dropped, made unique with order kept: (ptr, rows)."""
+    row_of = {}
+    for i, g in enumerate(gene_names):
+        row_of.setdefault(str(g), i)
+    ptr, rows = [0], []
+    for members in pathways.values():
+        rows.extend(dict.fromkeys(row_of[str(m)] for m in members if str(m) in row_of))
+        ptr.append(len(rows))
+    return np.asarray(ptr, dtype=np.int64), np.asarray(rows, dtype=np.int32)
+
+
+def fgsea(pathways: dict, stats, nsim: int = 1000, minSize=1, maxSize=np.inf, seed: int = 180582, names=None, ctx: Context | None = None):
+    """``fgsea(pathways, stats, minSize, maxSize, gseaParam = 0)`` for one ranked vector: ``stats`` is a ``pandas.Series`` indexed
+    by gene name, or an array plus ``names``.  Returns a ``pandas.DataFrame`` ``pathway, pval, padj, ES, NES, size`` of the tested
+    pathways in input order; ``padj = p.adjust(pval, "BH")`` over them.  Relaxed contract: see :func:`gsea`."""
+    import pandas as pd
+
+    if names is None:
+        if not isinstance(stats, pd.Series):
+            raise ValueError("stats must be a pandas Series indexed by gene name, or an array with names=")
+        names = stats.index
+    v = np.asarray(stats, dtype=np.float64)
+    if v.ndim != 1 or len(names) != len(v):
+        raise ValueError("stats must hold one value per name")
+    ptr, rows = _pathway_csr(pathways, names)
+    r = gsea(v, ptr, rows, nsim, minSize, maxSize, seed, False, ctx)
+    t = np.flatnonzero(r["tested"])
+    pv = r["pval"][t, 0]
+    return pd.DataFrame({"pathway": [n for n, k in zip(pathways, r["tested"]) if k], "pval": pv, "padj": p_adjust_fdr(pv), "ES": r["es"][t, 0],
+                         "NES": r["nes"][t, 0], "size": r["size"][t]})
+
+
+def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = False, convertHu2Mm: bool = False, nt: int = 2, minSize=15,
+            maxSize=np.inf, verbose: bool = True, seed: int = 180582, method: str = "GSEA", *, pathways=None, gene_names=None, gene_map=None,
+            ctx: Context | None = None) -> dict:
+    """``runGSEA(data, gmt.file, nsim, convertToEns, convertHu2Mm, nt, minSize, maxSize, verbose, seed, method)`` of the
+    reference (R/pathwayAnalisys.R:65-96): gene-set enrichment of every cluster's ``data["cluster.gene.rnk"]`` column, all
+    clusters in one device call (:func:`gsea`; the reference calls ``fgseaMultilevel(..., gseaParam = 0)`` per cluster).
+
+    ``pathways``: a dict ``{name: [genes]}`` in place of ``gmt_file`` (read by :func:`gmt_pathways`, with ``gene_map`` for the
+    conversions).  ``gene_names``: one name per row of ``data["gficf"]``; default ``data["gene_names"]``, else
+    ``data["genes"]`` as strings.  Members are matched by name, made unique, unmatched ones dropped, as fgsea does.
+    ``convertToEns`` defaults to False here (True in the reference, where it asks biomaRt): the one default that differs.
+    ``nt`` is accepted for signature compatibility.  ``method="GSVA"`` (GSVA / limma) is not provided.
+
+    ``data["gsea"]`` becomes ``{"pathways", "es", "nes", "pval", "fdr", "stat"}``: the four tables are ``pandas.DataFrame``
+    (index: pathway names, columns: ``data["cluster.labels"]``) holding zeros where a pathway was not tested, ``fdr`` is
+    Benjamini-Hochberg per cluster over the tested pathways, ``stat`` lists ``pathway, size`` of the tested pathways.
+    Relaxed contract (include/gficf_gsea.h): ES and NES are fgsea's; the p-value is ``fgseaSimple``'s with ``nsim``
+    permutations, not the multilevel estimate; the random bits are this library's.
+    """
+    import pandas as pd
+
+    if data.get("cluster.gene.rnk") is None:
+        raise ValueError("Please run clustcell function first")
+    if method not in ("GSEA", "GSVA"):
+        raise ValueError("'method' should be one of \"GSEA\", \"GSVA\"")
+    if method == "GSVA":
+        raise NotImplementedError("method=\"GSVA\" (GSVA scores and limma models) is not provided")
+    tsmessage("Choosen method is GSEA...", verbose=verbose)
+    if pathways is None:
+        if gmt_file is None:
+            raise ValueError("give gmt_file or pathways=")
+        pathways = gmt_pathways(gmt_file, convertToEns, convertHu2Mm, verbose, gene_map)
+    else:
+        pathways = {str(k): list(v) for k, v in pathways.items() if len(v) > 0}
+    stats = np.asarray(data["cluster.gene.rnk"], dtype=np.float64)
+    if gene_names is None:
+        gene_names = data.get("gene_names")
+    if gene_names is None and data.get("genes") is not None:
+        gene_names = np.asarray(data["genes"]).astype(str)
+    if gene_names is None or len(gene_names) != stats.shape[0]:
+        raise ValueError("gene_names must hold one name per row of data[\"cluster.gene.rnk\"]")
+    labels = data.get("cluster.labels")
+    labels = list(range(stats.shape[1])) if labels is None else list(labels)
+    ptr, rows = _pathway_csr(pathways, gene_names)
+    tsmessage(f"GSEA of {len(pathways)} pathways in {stats.shape[1]} clusters, {int(nsim)} permutations", verbose=verbose)
+    r = gsea(stats, ptr, rows, nsim, minSize, maxSize, seed, False, ctx)
+    t = np.flatnonzero(r["tested"])
+    fdr = np.zeros_like(r["pval"])
+    for c in range(stats.shape[1]):
+        fdr[t, c] = p_adjust_fdr(r["pval"][t, c])
+    names = list(pathways)
+    tab = {k: pd.DataFrame(v, index=names, columns=labels) for k, v in (("es", r["es"]), ("nes", r["nes"]), ("pval", r["pval"]), ("fdr", fdr))}
+    data["gsea"] = {"pathways": pathways, **tab,
+                    "stat": pd.DataFrame({"pathway": [names[i] for i in t], "size": r["size"][t]})}
+    tsmessage("Done!", verbose=verbose)
+    return data
+
+
 def run_modularity_clustering(SNN, modularity: int = 1, resolution: float = 0.8, algorithm: int = 1, n_start: int = 10,
                               n_iter: int = 10, random_seed: int = 0, print_output: bool = False, ctx: Context | None = None):
     """``RunModularityClustering(SNN, modularity, resolution, algorithm, n.start, n.iter, random.seed, print.output)``
@@ -1843,6 +2011,30 @@ class HipOps:
         from . import _markers_lib
 
         check(_markers_lib.load().gficf_cluster_markers_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def gsea_workspace_bytes(G: int, C: int, P: int, n_members: int, D: int, nsim: int) -> int:
+        """Device scratch of ``gsea`` (libgficf_gsea.so)."""
+        from . import _gsea_lib
+
+        return int(_gsea_lib.load().gficf_gsea_workspace_bytes(int(G), int(C), int(P), int(n_members), int(D), int(nsim)))
+
+    def gsea(self, G, C, stats, ptr, members, sizes, size_idx, nsim, seed, ws, es, nes, pval, null=None):
+        """Gene-set enrichment on device-resident tensors (stats: (C, G) float64 == column-major G x C; ptr int64 of P + 1,
+        members int32; sizes int32: the D distinct tested sizes, ascending; size_idx int32 per pathway, -1 = not tested; ws uint8
+        of ``gsea_workspace_bytes``); es, nes, pval: (C, P) float64 == column-major P x C; null: (D, nsim) or None.  Enqueues
+        only: call ``gsea_sync(ws)`` to wait and to collect the deferred input errors."""
+        from . import _gsea_lib
+
+        check(_gsea_lib.load().gficf_gsea_device(self._bind(), int(G), int(C), _tptr(stats), int(ptr.numel()) - 1, _tptr(ptr), _tptr(members),
+                                                 int(members.numel()), int(sizes.numel()), _tptr(sizes), _tptr(size_idx), int(nsim),
+                                                 int(seed) & 0xFFFFFFFF, _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(es), _tptr(nes),
+                                                 _tptr(pval), _tptr(null)))
+
+    def gsea_sync(self, ws):
+        from . import _gsea_lib
+
+        check(_gsea_lib.load().gficf_gsea_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
