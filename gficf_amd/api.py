@@ -1305,7 +1305,7 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     import pandas as pd
 
     if reduction == "tsne":
-        raise NotImplementedError("reduction='tsne' (Rtsne) is not provided: use 'tumap' or 'umap'")
+        raise NotImplementedError("reduction='tsne' (Rtsne) is not provided by runReduction: use 'tumap' or 'umap', or call runTsne")
     if reduction not in REDUCTIONS:
         raise ValueError(f"reduction must be one of {REDUCTIONS} ('tsne' is not provided)")
     unknown = sorted(set(kw) - set(_REDUCTION_KW))
@@ -1334,6 +1334,252 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     data["reduction"] = reduction
     if ret_model_pred:
         data["uwot"] = r
+    return data
+
+
+# ------------------------------------------------------------------ t-SNE (libgficf_tsne.so)
+_TSNE_KW = {"perplexity": 30, "theta": 0.5, "max_iter": 1000, "Y_init": None, "normalize": True, "stop_lying_iter": None,
+            "mom_switch_iter": None, "momentum": 0.5, "final_momentum": 0.8, "eta": 200, "exaggeration_factor": 12, "ret_P": False,
+            "ret_nn": False}
+
+
+def _tsne_k(perplexity, N: int) -> int:
+    """The columns of the neighbour table for ``perplexity`` (floor(3 perplexity) + 1), after the checks of include/gficf_tsne.h
+    that need no device: the library would say the same."""
+    perplexity = float(perplexity)
+    if not perplexity > 0 or not np.isfinite(perplexity):
+        raise ValueError("perplexity must be positive")
+    if N - 1 < 3 * perplexity:
+        raise ValueError(f"perplexity = {perplexity:g} is too large for the number of samples ({N}): N - 1 >= 3 perplexity")
+    K = int(np.floor(3 * perplexity))
+    if K + 1 > _lib.KNN_MAX_K:
+        raise GficfError(6, f"perplexity = {perplexity:g} needs {K + 1} neighbours, beyond {_lib.KNN_MAX_K} (perplexity < 42.34)")
+    if K < 1:
+        raise ValueError(f"perplexity = {perplexity:g} names no neighbour (floor(3 perplexity) = 0)")
+    return K + 1
+
+
+def _tsne_csr(P):
+    """(N, indptr int64, indices int32, data float32) of ``P``: a scipy sparse matrix (taken as CSR with sorted columns), or the
+    three arrays themselves as ``(indptr, indices, data)``, which are handed to the library unchecked."""
+    import scipy.sparse as sp
+
+    if isinstance(P, tuple):
+        indptr, indices, data = P
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        return len(indptr) - 1, indptr, np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(data, dtype=np.float32)
+    P = sp.csr_matrix(P)
+    if P.shape[0] != P.shape[1]:
+        raise ValueError("P must be square")
+    if not P.has_sorted_indices:
+        P = P.sorted_indices()
+    return P.shape[0], P.indptr.astype(np.int64), np.ascontiguousarray(P.indices, dtype=np.int32), np.ascontiguousarray(P.data, dtype=np.float32)
+
+
+def _tsne_dev_csr(ops, P):
+    tc, dev = ops.torch, f"cuda:{ops.device}"
+    N, indptr, indices, data = _tsne_csr(P)
+    cap = int(len(indices))
+    if N < 1 or len(data) != cap:
+        raise ValueError("P needs at least one row, and as many values as columns")
+    rowptr = tc.from_numpy(indptr).to(dev)
+    col = tc.from_numpy(indices).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
+    val = tc.from_numpy(data).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
+    return N, cap, rowptr, col, val
+
+
+def _tsne_state(a, N: int, name: str, fill: float) -> np.ndarray:
+    if a is None:
+        return np.full((N, 2), fill, dtype=np.float32)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != (N, 2):
+        raise ValueError(f"{name} must be an N x 2 = {N} x 2 array")
+    return a
+
+
+def tsne_shape(N: int) -> dict:
+    """The decomposition of the repulsion kernel for ``N`` points (``gficf_tsne_shape``, a host query that depends on N only):
+    ``{"rows_per_block", "tile", "slices"}``.  ``tile`` is also T, the longest f32 accumulation chain (include/gficf_tsne.h)."""
+    from . import _tsne_lib
+
+    r, t, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(_tsne_lib.load().gficf_tsne_shape(int(N), ctypes.byref(r), ctypes.byref(t), ctypes.byref(s)))
+    return {"rows_per_block": r.value, "tile": t.value, "slices": s.value}
+
+
+def tsne_affinities(idx, dist, perplexity: float = 30, ret_cond: bool = False, device: int = 0):
+    """t-SNE's input similarities from a euclidean neighbour table as :func:`find_nn` returns it (``idx`` N x k, 1-based, column 0
+    the point itself; ``dist`` alike; the first ``floor(3 perplexity) + 1`` columns are used): the bisection for every row's
+    ``beta`` and the symmetrisation ``(Pc + Pc') / (2 N)`` (``gficf_tsne_affinities_device``, include/gficf_tsne.h).  Returns
+    ``(P, beta)``: the N x N scipy CSR matrix (float32, columns ascending, ``P == P.T`` bit for bit) and the float64 vector; with
+    ``ret_cond`` also ``Pc``, the N x floor(3 perplexity) float32 conditionals before the symmetrisation."""
+    import scipy.sparse as sp
+
+    idx, dist = np.asarray(idx), np.asarray(dist)
+    if idx.ndim != 2 or idx.shape != dist.shape:
+        raise ValueError("idx and dist must be N x k matrices of the same shape")
+    N = idx.shape[0]
+    k = _tsne_k(perplexity, N)
+    if idx.shape[1] < k:
+        raise ValueError(f"perplexity = {float(perplexity):g} needs a table of floor(3 perplexity) + 1 = {k} columns, got {idx.shape[1]}")
+    K = k - 1
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    d_idx = tc.from_numpy(np.ascontiguousarray(idx[:, :k].T, dtype=np.int32)).to(dev)    # (k, N) C-order == column-major N x k
+    d_dist = tc.from_numpy(np.ascontiguousarray(dist[:, :k].T, dtype=np.float32)).to(dev)
+    cap = 2 * N * K
+    ws = tc.empty(max(ops.tsne_affinities_workspace_bytes(N, k), 1), dtype=tc.uint8, device=dev)
+    rowptr = tc.empty(N + 1, dtype=tc.int64, device=dev)
+    col = tc.empty(cap, dtype=tc.int32, device=dev)
+    val = tc.empty(cap, dtype=tc.float32, device=dev)
+    nnz = tc.zeros(1, dtype=tc.int64, device=dev)
+    beta = tc.empty(N, dtype=tc.float64, device=dev)
+    pc = tc.empty((K, N), dtype=tc.float32, device=dev) if ret_cond else None
+    ops.tsne_affinities(d_idx, d_dist, N, k, perplexity, ws, rowptr, col, val, nnz, beta, pc)
+    ops.tsne_sync(ws)
+    n = int(nnz.item())
+    P = sp.csr_matrix((val[:n].cpu().numpy(), col[:n].cpu().numpy(), rowptr.cpu().numpy()), shape=(N, N))
+    if ret_cond:
+        return P, beta.cpu().numpy(), np.ascontiguousarray(pc.cpu().numpy().T)
+    return P, beta.cpu().numpy()
+
+
+def tsne_gradient(P, Y, exaggeration: float = 1.0, device: int = 0) -> dict:
+    """One evaluation of t-SNE's gradient at the coordinates ``Y`` (N x 2) over ``P`` (scipy sparse, or ``(indptr, indices,
+    data)``): ``gficf_tsne_gradient_device``, the exact repulsive field of all N^2 pairs.  Returns ``{"grad": N x 2 float32 (x
+    attr - rep / Z: Rtsne's form, without the factor 4), "rep": N x 2 float32 (un-normalised), "Z": float, "kl": float}``."""
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    N, cap, rowptr, col, val = _tsne_dev_csr(ops, P)
+    d_Y = tc.from_numpy(_tsne_state(Y, N, "Y", 0.0)).to(dev)
+    ws = tc.empty(max(ops.tsne_layout_workspace_bytes(N, cap), 1), dtype=tc.uint8, device=dev)
+    dC = tc.empty((N, 2), dtype=tc.float32, device=dev)
+    rep = tc.empty((N, 2), dtype=tc.float32, device=dev)
+    zk = tc.zeros(2, dtype=tc.float64, device=dev)
+    ops.tsne_gradient(N, rowptr, col, val, cap, d_Y, exaggeration, ws, dC, rep, zk[0:1], zk[1:2])
+    ops.tsne_sync(ws)
+    zk = zk.cpu().numpy()
+    return {"grad": dC.cpu().numpy(), "rep": rep.cpu().numpy(), "Z": float(zk[0]), "kl": float(zk[1])}
+
+
+def tsne_layout(P, Y, max_iter: int = 1000, iter_begin: int = 0, iter_end=None, uY=None, gains=None, stop_lying_iter: int = 250,
+                mom_switch_iter: int = 250, momentum: float = 0.5, final_momentum: float = 0.8, eta: float = 200,
+                exaggeration_factor: float = 12, ret_state: bool = False, ret_kl: bool = False, device: int = 0):
+    """Iterations ``[iter_begin, iter_end)`` of ``max_iter`` of the t-SNE layout over ``P`` from the coordinates ``Y`` (N x 2):
+    ``gficf_tsne_layout_device``, the update rule of include/gficf_tsne.h.  ``uY`` (the velocity, default 0) and ``gains`` (default
+    1) are the rest of the state.  Returns the N x 2 float32 coordinates, or with ``ret_state`` the tuple ``(Y, uY, gains)``;
+    handing the three back and running ``[a, n)`` after ``[0, a)`` gives the bits of ``[0, n)``.  ``ret_kl`` appends the KL
+    divergence of the coordinates returned."""
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    N, cap, rowptr, col, val = _tsne_dev_csr(ops, P)
+    iter_end = int(max_iter) if iter_end is None else int(iter_end)
+    d_Y = tc.from_numpy(_tsne_state(Y, N, "Y", 0.0)).to(dev)
+    d_u = tc.from_numpy(_tsne_state(uY, N, "uY", 0.0)).to(dev)
+    d_g = tc.from_numpy(_tsne_state(gains, N, "gains", 1.0)).to(dev)
+    ws = tc.empty(max(ops.tsne_layout_workspace_bytes(N, cap), 1), dtype=tc.uint8, device=dev)
+    kl = tc.zeros(1, dtype=tc.float64, device=dev) if ret_kl else None
+    ops.tsne_layout(N, rowptr, col, val, cap, max_iter, iter_begin, iter_end, stop_lying_iter, mom_switch_iter, momentum, final_momentum, eta,
+                    exaggeration_factor, d_Y, d_u, d_g, ws, kl)
+    ops.tsne_sync(ws)
+    out = (d_Y.cpu().numpy(), d_u.cpu().numpy(), d_g.cpu().numpy()) if ret_state else d_Y.cpu().numpy()
+    if ret_kl:
+        return (*out, float(kl.item())) if ret_state else (out, float(kl.item()))
+    return out
+
+
+def Rtsne(X, dims: int = 2, perplexity: float = 30, theta: float = 0.5, max_iter: int = 1000, Y_init=None, normalize: bool = True,
+          stop_lying_iter=None, mom_switch_iter=None, momentum: float = 0.5, final_momentum: float = 0.8, eta: float = 200,
+          exaggeration_factor: float = 12, pca: bool = False, seed: int = 18051982, ret_P: bool = False, ret_nn: bool = False,
+          ctx: Context | None = None) -> dict:
+    """``Rtsne::Rtsne(X, dims = 2, pca = F, ...)`` on the device in one call of the C ABI (``gficf_tsne_host``): exact euclidean
+    neighbour search (``floor(3 perplexity)`` neighbours), the perplexity graph, ``max_iter`` iterations of the layout with the
+    EXACT repulsion of all N^2 pairs.  RELAXED CONTRACT (include/gficf_tsne.h): the algorithm and its objective are Rtsne's, the
+    random bits are not: without ``Y_init`` the start is ``default_rng(seed).standard_normal((N, 2)) * 1e-4``.
+
+    ``normalize`` is Rtsne's ``normalize_input`` (the columns centred, then everything divided by the largest magnitude), done
+    on the host.  ``theta`` is accepted and recorded: the repulsion is exact whatever its value.  ``stop_lying_iter`` and
+    ``mom_switch_iter`` default to 250, or to 0 when ``Y_init`` is given, as in Rtsne.  ``dims != 2`` and ``pca=True`` (Rtsne's
+    own PCA step; the reference passes ``pca = F``) raise ``ValueError``.  Duplicate rows are not checked for (Rtsne refuses
+    them): they are harmless here.  Returns ``{"Y": N x 2, "N", "perplexity", "costs": the final KL divergence, "theta",
+    "max_iter", "eta", "stop_lying_iter", "mom_switch_iter", "momentum", "final_momentum", "exaggeration_factor", "P": scipy CSR
+    or None, "nn": {"idx", "dist"} or None}``."""
+    import scipy.sparse as sp
+
+    from . import _tsne_lib
+
+    if int(dims) != 2:
+        raise ValueError("dims must be 2: the layout is two-dimensional")
+    if pca:
+        raise ValueError("pca=True (Rtsne's own PCA step) is not provided: pass the components (the reference calls Rtsne with pca = F)")
+    X = np.array(X, dtype=np.float64, order="F")
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-d matrix")
+    N, d = X.shape
+    k = _tsne_k(perplexity, N)
+    given = Y_init is not None
+    if given:
+        Y0 = np.asfortranarray(Y_init, dtype=np.float64)
+        if Y0.shape != (N, 2):
+            raise ValueError(f"Y_init must be an N x 2 = {N} x 2 array")
+    else:
+        Y0 = np.asfortranarray(np.random.default_rng(seed).standard_normal((N, 2)) * 1e-4)
+    stop_lying_iter = (0 if given else 250) if stop_lying_iter is None else int(stop_lying_iter)
+    mom_switch_iter = (0 if given else 250) if mom_switch_iter is None else int(mom_switch_iter)
+    if normalize:
+        X -= X.mean(axis=0)
+        top = np.abs(X).max()
+        if top > 0:
+            X /= top
+    emb = np.zeros((2, N), dtype=np.float64)                  # C-order (2, N) == column-major N x 2
+    kl = np.zeros(1, dtype=np.float64)
+    cap = 2 * N * (k - 1)
+    rowptr = col = val = nnz = idx = dist = None
+    if ret_P:
+        rowptr, col, val, nnz = np.zeros(N + 1, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(1, np.int64)
+    if ret_nn:
+        idx, dist = np.zeros((k, N), np.int32), np.zeros((k, N), np.float32)
+    ctx = ctx or default_context()
+    check(_tsne_lib.load().gficf_tsne_host(ctx.handle, _np_ptr(X), N, d, max(N, 1), float(perplexity), int(max_iter), stop_lying_iter,
+                                           mom_switch_iter, float(momentum), float(final_momentum), float(eta), float(exaggeration_factor),
+                                           _np_ptr(Y0), _np_ptr(emb), _np_ptr(kl), _np_ptr(rowptr), _np_ptr(col), _np_ptr(val), _np_ptr(nnz),
+                                           _np_ptr(idx), _np_ptr(dist)))
+    P = nn = None
+    if ret_P:
+        n = int(nnz[0])
+        P = sp.csr_matrix((val[:n].copy(), col[:n].copy(), rowptr), shape=(N, N))
+    if ret_nn:
+        nn = {"idx": np.ascontiguousarray(idx.T), "dist": np.ascontiguousarray(dist.T, dtype=np.float64)}
+    return {"Y": np.ascontiguousarray(emb.T), "N": N, "perplexity": float(perplexity), "costs": float(kl[0]), "theta": float(theta),
+            "max_iter": int(max_iter), "eta": float(eta), "stop_lying_iter": stop_lying_iter, "mom_switch_iter": mom_switch_iter,
+            "momentum": float(momentum), "final_momentum": float(final_momentum), "exaggeration_factor": float(exaggeration_factor), "P": P,
+            "nn": nn}
+
+
+def runTsne(data: dict, seed: int = 18051982, verbose: bool = True, ctx: Context | None = None, **kw) -> dict:
+    """The ``reduction = "tsne"`` branch of the reference's ``runReduction`` (R/dimensinalityReduction.R:175-177:
+    ``Rtsne::Rtsne(X = data$pca$cells, dims = 2, pca = F, max_iter = 1000)``) on the device (:func:`Rtsne`, whose further
+    arguments are accepted here with Rtsne's defaults: ``perplexity=30, theta=0.5, max_iter=1000, Y_init=None, normalize=True,
+    stop_lying_iter=None, mom_switch_iter=None, momentum=0.5, final_momentum=0.8, eta=200, exaggeration_factor=12, ret_P=False,
+    ret_nn=False``).  ``data["embedded"]`` becomes a pandas DataFrame with the columns ``X`` and ``Y``, ``data["reduction"]``
+    ``"tsne"`` and ``data["uwot"]`` None, as the reference leaves them; ``data["tsne"]`` keeps the rest of what :func:`Rtsne`
+    returned.  A ``data`` without ``data["pca"]`` raises ``NotImplementedError`` (the reference then embeds the densified
+    ``t(gficf)``)."""
+    import pandas as pd
+
+    unknown = sorted(set(kw) - set(_TSNE_KW))
+    if unknown:
+        raise TypeError(f"runTsne: unknown argument(s) {unknown}")
+    if data.get("pca") is None:
+        raise NotImplementedError("runTsne without data['pca'] (the reference embeds the densified t(gficf)) is not provided: "
+                                  "run runPCA or runLSA first")
+    cells = np.asarray(data["pca"]["cells"], dtype=np.float64)
+    tsmessage(f"Running tsne on {cells.shape[0]} cells, {cells.shape[1]} components", verbose=verbose)
+    r = Rtsne(cells, dims=2, pca=False, seed=seed, ctx=ctx, **dict(_TSNE_KW, **kw))
+    data["embedded"] = pd.DataFrame(r.pop("Y"), columns=["X", "Y"])
+    data["reduction"] = "tsne"
+    data["uwot"] = None
+    data["tsne"] = r
     return data
 
 
@@ -1481,7 +1727,8 @@ def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: boo
     import scipy.sparse as sp
 
     if data.get("reduction") == "tsne":
-        raise NotImplementedError("embedNewCells after reduction='tsne' (the reference re-runs Rtsne) is not provided")
+        raise NotImplementedError("embedNewCells after reduction='tsne' (the reference re-runs Rtsne) is not provided: "
+                                  "run runTsne on the old and the new cells together")
     if data.get("uwot") is None:
         raise ValueError("embedNewCells needs the trained model: run runReduction(ret_model_pred=True) first")
     unknown = sorted(set(kw) - set(_TRANSFORM_KW))
@@ -2125,6 +2372,58 @@ class HipOps:
         from . import _umap_lib
 
         check(_umap_lib.load().gficf_umap_sync(self._bind(), _tptr(ws)))
+
+    # -- t-SNE (libgficf_tsne.so)
+    @staticmethod
+    def tsne_affinities_workspace_bytes(N: int, k: int) -> int:
+        """Device scratch of ``tsne_affinities`` (libgficf_tsne.so)."""
+        from . import _tsne_lib
+
+        return int(_tsne_lib.load().gficf_tsne_affinities_workspace_bytes(int(N), int(k)))
+
+    def tsne_affinities(self, idx_cm, dist_cm, N, k, perplexity, ws, rowptr, col, val, nnz, beta=None, pc=None):
+        """t-SNE's P from the search's own output (idx_cm int32 / dist_cm float32: (k, ld) == column-major N x k, k = floor(3
+        perplexity) + 1, euclidean): rowptr int64 N + 1, col int32 / val float32 of at least 2 N (k - 1) entries, nnz int64 (1),
+        beta float64 N or None, pc (the conditionals, (k - 1, N) float32) or None.  Enqueues only: ``tsne_sync(ws)`` waits and
+        collects the deferred input errors."""
+        from . import _tsne_lib
+
+        ld = idx_cm.shape[1] if idx_cm.dim() == 2 else N
+        check(_tsne_lib.load().gficf_tsne_affinities_device(self._bind(), _tptr(idx_cm), _tptr(dist_cm), int(N), int(k), int(ld), float(perplexity),
+                                                            _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(rowptr), _tptr(col), _tptr(val),
+                                                            int(min(col.numel(), val.numel())), _tptr(nnz), _tptr(beta), _tptr(pc)))
+
+    @staticmethod
+    def tsne_layout_workspace_bytes(N: int, capacity: int) -> int:
+        """Device scratch of ``tsne_gradient`` and ``tsne_layout``."""
+        from . import _tsne_lib
+
+        return int(_tsne_lib.load().gficf_tsne_layout_workspace_bytes(int(N), int(capacity)))
+
+    def tsne_gradient(self, N, rowptr, col, val, capacity, Y, exaggeration, ws, dC, rep=None, Z=None, kl=None):
+        """dC ((N, 2) float32) = exaggeration x attr - rep / Z at Y ((N, 2) float32) over P; rep (N, 2) float32 or None, Z float64
+        (1), kl float64 (1) or None.  Enqueues only."""
+        from . import _tsne_lib
+
+        check(_tsne_lib.load().gficf_tsne_gradient_device(self._bind(), int(N), _tptr(rowptr), _tptr(col), _tptr(val), int(capacity), _tptr(Y),
+                                                          float(exaggeration), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(dC),
+                                                          _tptr(rep), _tptr(Z), _tptr(kl)))
+
+    def tsne_layout(self, N, rowptr, col, val, capacity, max_iter, iter_begin, iter_end, stop_lying_iter, mom_switch_iter, momentum,
+                    final_momentum, eta, exaggeration_factor, Y, uY, gains, ws, kl=None):
+        """Iterations [iter_begin, iter_end) of max_iter in place on Y, uY and gains ((N, 2) float32 each); kl float64 (1) or None.
+        Three launches per iteration; enqueues only."""
+        from . import _tsne_lib
+
+        check(_tsne_lib.load().gficf_tsne_layout_device(self._bind(), int(N), _tptr(rowptr), _tptr(col), _tptr(val), int(capacity), int(max_iter),
+                                                        int(iter_begin), int(iter_end), int(stop_lying_iter), int(mom_switch_iter),
+                                                        float(momentum), float(final_momentum), float(eta), float(exaggeration_factor), _tptr(Y),
+                                                        _tptr(uY), _tptr(gains), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(kl)))
+
+    def tsne_sync(self, ws):
+        from . import _tsne_lib
+
+        check(_tsne_lib.load().gficf_tsne_sync(self._bind(), _tptr(ws)))
 
     # -- new cells (libgficf_transform.so); every *_workspace_bytes scratch begins with the status word transform_sync reads
     @staticmethod
