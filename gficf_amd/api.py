@@ -1154,11 +1154,13 @@ def find_ab_params(spread: float = 1.0, min_dist: float = 0.01):
 def umap_init(init, pca_cells, N: int, seed: int) -> np.ndarray:
     """The initial coordinates of :func:`runReduction`, N x 2 float64.  ``"pca"``: the first two columns of ``pca_cells`` scaled
     to a largest magnitude of 10, plus normal noise of standard deviation 1e-4 from ``default_rng(seed)``; ``"random"``: uniform
-    on [-10, 10) from the same generator; an N x 2 array is taken as it is.  ``"spectral"`` (uwot's default) is not provided."""
+    on [-10, 10) from the same generator; an N x 2 array is taken as it is.  ``"spectral"`` (uwot's default) needs the graph, not
+    the cells: :func:`spectral_init` computes it, and :func:`umap` takes the string."""
     if isinstance(init, str):
         if init == "spectral":
-            raise NotImplementedError("init='spectral' (uwot's default) is not provided: pass init='pca' (the default here), "
-                                      "'random' or an N x 2 array")
+            raise NotImplementedError("init='spectral' (uwot's default) is not wired into runReduction: call gficf_amd.umap(..., "
+                                      "init='spectral') or pass init=gficf_amd.spectral_init(graph); init='normlaplacian', 'pca' (the "
+                                      "default here), 'random' and an N x 2 array are taken")
         if init not in ("pca", "random"):
             raise ValueError("init must be 'pca', 'random' or an N x 2 array")
         rng = np.random.default_rng(seed)
@@ -1243,13 +1245,178 @@ def umap_layout(P, init, n_epochs: int, a: float = 1.0, b: float = 1.0, learning
     return d_Y.cpu().numpy()
 
 
+def _spectral_csr(P):
+    """P as square scipy CSR with sorted columns."""
+    import scipy.sparse as sp
+
+    P = sp.csr_matrix(P)
+    if P.shape[0] != P.shape[1]:
+        raise ValueError("P must be square")
+    if P.shape[0] < 1:
+        raise ValueError("P has no vertices")
+    if not P.has_sorted_indices:
+        P = P.sorted_indices()
+    return P
+
+
+def _spectral_dev_csr(ops, P, device):
+    tc, dev = ops.torch, f"cuda:{device}"
+    cap = int(P.nnz)
+    rowptr = tc.from_numpy(P.indptr.astype(np.int64)).to(dev)
+    col = tc.from_numpy(np.ascontiguousarray(P.indices, dtype=np.int32)).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
+    val = tc.from_numpy(np.ascontiguousarray(P.data, dtype=np.float32)).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
+    return rowptr, col, val, cap
+
+
+def graph_components(P, ret_rounds: bool = False, device: int = 0):
+    """The connected components of the graph ``P`` (scipy sparse, square; an entry (i, j) joins i and j whether or not (j, i) is
+    stored): ``gficf_graph_components_device`` (include/gficf_spectral.h), hook and pointer-jump on the device.  Returns
+    ``(labels, n)``: ``labels[i]`` (int32) is the smallest vertex id of i's component, ``n`` the number of components; with
+    ``ret_rounds`` also the number of rounds it took."""
+    P = _spectral_csr(P)
+    N = P.shape[0]
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    rowptr, col, _, cap = _spectral_dev_csr(ops, P, device)
+    labels = tc.empty(N, dtype=tc.int32, device=dev)
+    info = tc.zeros(2, dtype=tc.int64, device=dev)
+    ws = tc.empty(max(ops.graph_components_workspace_bytes(N), 1), dtype=tc.uint8, device=dev)
+    ops.graph_components(N, rowptr, col, cap, labels, info, ws)
+    info = info.cpu().numpy()
+    if ret_rounds:
+        return labels.cpu().numpy(), int(info[0]), int(info[1])
+    return labels.cpu().numpy(), int(info[0])
+
+
+def _spectral_args(N: int, ndim, m, tol, max_restarts, start):
+    """The checks of include/gficf_spectral.h that need no device (the library would say the same); the start block or None."""
+    from . import _spectral_lib
+
+    ndim, m, max_restarts = int(ndim), int(m), int(max_restarts)
+    if not 1 <= ndim <= _spectral_lib.MAX_NDIM:
+        raise ValueError(f"ndim = {ndim} outside [1, {_spectral_lib.MAX_NDIM}]")
+    if N <= ndim:
+        raise ValueError(f"N = {N} vertices for ndim = {ndim}: N must exceed ndim")
+    if not 2 * ndim + 2 <= m <= _spectral_lib.MAX_M:
+        raise ValueError(f"m = {m} outside [2 ndim + 2, {_spectral_lib.MAX_M}] = [{2 * ndim + 2}, {_spectral_lib.MAX_M}]")
+    if not (float(tol) > 0 and np.isfinite(float(tol))):
+        raise ValueError("tol must be positive and finite")
+    if max_restarts < 0:
+        raise ValueError("max_restarts must not be negative")
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        if start.shape != (N, ndim):
+            raise ValueError(f"start must be an N x ndim = {N} x {ndim} array")
+        if not np.isfinite(start).all():
+            raise ValueError("start must be finite")
+    return ndim, m, max_restarts, start
+
+
+def _spectral_solve(P, ndim=2, start=None, seed=18051982, tol=1e-4, m=32, max_restarts=200, device: int = 0) -> dict:
+    """:func:`spectral_embedding` without its verdicts: a disconnected graph comes back with ``vectors`` None."""
+    P = _spectral_csr(P)
+    N = P.shape[0]
+    ndim, m, max_restarts, start = _spectral_args(N, ndim, m, tol, max_restarts, start)
+    if start is None:
+        start = np.random.default_rng(seed).standard_normal((N, ndim))
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    rowptr, col, val, cap = _spectral_dev_csr(ops, P, device)
+    d_start = tc.from_numpy(start).to(dev)
+    theta = tc.full((ndim,), float("nan"), dtype=tc.float64, device=dev)
+    resid = tc.full((ndim,), float("nan"), dtype=tc.float64, device=dev)
+    vectors = tc.empty((N, ndim), dtype=tc.float64, device=dev)
+    info = tc.zeros(4, dtype=tc.int64, device=dev)
+    ws = tc.empty(max(ops.spectral_workspace_bytes(N, cap, ndim, m), 1), dtype=tc.uint8, device=dev)
+    ops.spectral(N, rowptr, col, val, cap, ndim, d_start, tol, m, max_restarts, ws, theta, resid, vectors, info)
+    info = info.cpu().numpy()
+    r = {"vectors": None, "values": None, "laplacian_values": None, "residuals": None, "n_components": int(info[0]),
+         "restarts": int(info[1]), "multiplications": int(info[2]), "converged": bool(info[3])}
+    if r["n_components"] == 1:
+        th = theta.cpu().numpy()
+        r.update(vectors=vectors.cpu().numpy(), values=th, laplacian_values=1.0 - th, residuals=resid.cpu().numpy())
+    return r
+
+
+def spectral_embedding(P, ndim: int = 2, start=None, seed: int = 18051982, tol: float = 1e-4, m: int = 32, max_restarts: int = 200,
+                       device: int = 0) -> dict:
+    """The ``ndim`` lowest non-trivial eigenvectors of the normalised Laplacian of the symmetric graph ``P`` (scipy sparse, as
+    :func:`fuzzy_simplicial_set` returns it): ``gficf_spectral_device`` (include/gficf_spectral.h), a block Krylov subspace with
+    thick restart in f64 on S = D^-1/2 P D^-1/2, in the complement of its trivial eigenvector.  ``start``: the N x ndim start block
+    (default: standard normal from ``default_rng(seed)``); ``tol``: the bound on ``|S x - theta x| / |theta|`` (uwot's 1e-4); ``m``:
+    the columns of the basis; ``max_restarts``.  Returns ``{"vectors": N x ndim float64 (unit columns, the largest-magnitude entry of
+    each positive), "values": theta, "laplacian_values": 1 - theta, "residuals", "n_components", "restarts", "multiplications",
+    "converged"}``.  Raises ``ValueError`` naming the number of components when the graph is disconnected; warns when the
+    residuals do not meet ``tol`` after ``max_restarts`` restarts (what it has is returned)."""
+    r = _spectral_solve(P, ndim, start, seed, tol, m, max_restarts, device)
+    if r["n_components"] > 1:
+        raise ValueError(f"the graph has {r['n_components']} connected components: its Laplacian eigenvectors are not an embedding "
+                         "(see graph_components)")
+    if not r["converged"]:
+        warnings.warn(f"spectral_embedding: not converged after {r['restarts']} restarts (residuals {r['residuals']}, tol {tol})")
+    return r
+
+
+def _spectral_coordinates(vectors, rng, jitter: bool) -> np.ndarray:
+    Y = np.array(vectors, dtype=np.float64)
+    if jitter:
+        top = np.abs(Y).max()
+        if top > 0:
+            Y *= 10.0 / top
+        Y = Y + rng.normal(0.0, 1e-4, size=Y.shape)
+    return Y
+
+
+def spectral_init(P, seed: int = 18051982, jitter: bool = True, device: int = 0, **solver_kw) -> np.ndarray:
+    """uwot's spectral start of the layout from the fuzzy graph ``P``, N x 2 float64: the two vectors of
+    :func:`spectral_embedding`; with ``jitter`` (uwot's ``"spectral"``) scaled to a largest magnitude of 10 plus N(0, 1e-4) noise,
+    the scaling of :func:`umap_init`'s ``"pca"``; without (uwot's ``"normlaplacian"``) the raw unit vectors.  One
+    ``default_rng(seed)`` draws the start block first and the noise second.  ``solver_kw``: ``tol``, ``m``, ``max_restarts``."""
+    P = _spectral_csr(P)
+    rng = np.random.default_rng(seed)
+    if P.shape[0] <= 2:
+        raise ValueError(f"N = {P.shape[0]} vertices for ndim = 2: N must exceed ndim")
+    start = rng.standard_normal((P.shape[0], 2))
+    r = spectral_embedding(P, 2, start=start, device=device, **solver_kw)
+    return _spectral_coordinates(r["vectors"], rng, jitter)
+
+
+SPECTRAL_INITS = ("spectral", "normlaplacian")
+
+
+def _umap_spectral(X, init, k, metric, n_epochs, learning_rate, a, b, negative_sample_rate, repulsion_strength, set_op_mix_ratio, local_connectivity,
+                   seed, ret_graph, ret_nn, ctx) -> dict:
+    """:func:`umap` from a spectral start: the stages one after the other (their bits are the chained call's)."""
+    N = X.shape[0]
+    nn = find_nn(X, k, True, metric, ctx=ctx)
+    P = fuzzy_simplicial_set(nn["idx"], nn["dist"], set_op_mix_ratio, local_connectivity)[0]
+    rng = np.random.default_rng(seed)
+    r = _spectral_solve(P, 2, start=rng.standard_normal((N, 2)))
+    if r["n_components"] > 1:
+        warnings.warn(f"found more than one component ({r['n_components']}) in the graph: falling back to init='pca'")
+        Y0 = umap_init("pca", X, N, seed)
+    else:
+        if not r["converged"]:
+            warnings.warn(f"spectral initialisation not converged after {r['restarts']} restarts (residuals {r['residuals']})")
+        Y0 = _spectral_coordinates(r["vectors"], rng, init == "spectral")
+    Y = umap_layout(P, Y0, n_epochs, a, b, learning_rate, negative_sample_rate, repulsion_strength, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return {"embedding": Y.astype(np.float64), "graph": P if ret_graph else None,
+            "nn": {"idx": nn["idx"], "dist": np.asarray(nn["dist"], dtype=np.float64)} if ret_nn else None, "a": float(a), "b": float(b),
+            "n_neighbors": k, "metric": metric, "n_epochs": int(n_epochs), "seed": int(seed)}
+
+
 def umap(X, init, n_neighbors: int = 15, metric: str = "euclidean", n_epochs: int | None = None, learning_rate: float = 1.0, a: float = 1.0,
          b: float = 1.0, negative_sample_rate: int = 5, repulsion_strength: float = 1.0, set_op_mix_ratio: float = 1.0,
          local_connectivity: float = 1.0, seed: int = 18051982, ret_graph: bool = True, ret_nn: bool = True, ctx: Context | None = None) -> dict:
     """The embedding of the rows of ``X`` (N x d, d <= 128) in one call of the C ABI (``gficf_umap_host``): exact neighbour
     search with distances, fuzzy graph, ``n_epochs`` layout sweeps from ``init`` (N x 2), all on the device.  ``n_neighbors``
     counts the point itself, as uwot's does.  Returns ``{"embedding": N x 2, "graph": scipy CSR, "nn": {"idx", "dist"}, "a",
-    "b", "n_neighbors", "metric", "n_epochs", "seed"}`` (``graph`` / ``nn`` are None when not asked for)."""
+    "b", "n_neighbors", "metric", "n_epochs", "seed"}`` (``graph`` / ``nn`` are None when not asked for).
+
+    ``init`` may also be ``"spectral"`` (uwot's default: :func:`spectral_init` of the fuzzy graph) or ``"normlaplacian"`` (the same
+    without scaling and noise).  The call then runs the stages one after the other, :func:`find_nn`, :func:`fuzzy_simplicial_set`,
+    :func:`spectral_init`, :func:`umap_layout`, and returns the same dict.  A graph of more than one component warns, naming the
+    count, and starts from ``umap_init("pca", X, N, seed)`` as uwot does: the result is that call's, bit for bit."""
     import scipy.sparse as sp
 
     from . import _umap_lib
@@ -1260,12 +1427,17 @@ def umap(X, init, n_neighbors: int = 15, metric: str = "euclidean", n_epochs: in
     if X.ndim != 2:
         raise ValueError("X must be a 2-d matrix")
     N, d = X.shape
-    Y0 = np.asfortranarray(init, dtype=np.float64)
-    if Y0.shape != (N, 2):
-        raise ValueError(f"init must be an N x 2 = {N} x 2 array")
     k = int(n_neighbors)
     if n_epochs is None:
         n_epochs = 500 if N <= 10000 else 200
+    if isinstance(init, str):
+        if init not in SPECTRAL_INITS:
+            raise ValueError(f"init must be an N x 2 array or one of {SPECTRAL_INITS}")
+        return _umap_spectral(X, init, k, metric, n_epochs, learning_rate, a, b, negative_sample_rate, repulsion_strength, set_op_mix_ratio,
+                              local_connectivity, seed, ret_graph, ret_nn, ctx)
+    Y0 = np.asfortranarray(init, dtype=np.float64)
+    if Y0.shape != (N, 2):
+        raise ValueError(f"init must be an N x 2 = {N} x 2 array")
     emb = np.zeros((2, N), dtype=np.float64)                  # C-order (2, N) == column-major N x 2
     cap = max(2 * N * max(k, 0), 1)
     rowptr = col = val = nnz = idx = dist = None
@@ -1295,8 +1467,9 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     CONTRACT (include/gficf_umap.h): the algorithm and its objective are UMAP's, the random bits and the update order are not
     uwot's.  Further arguments, with uwot's meaning: ``n_neighbors=15, metric="euclidean", n_epochs=None`` (500 for N <= 10 000,
     else 200), ``learning_rate=1, min_dist=0.01, spread=1, a=None, b=None, negative_sample_rate=5, repulsion_strength=1,
-    set_op_mix_ratio=1, local_connectivity=1, init="pca"`` (:func:`umap_init`; uwot's default ``"spectral"`` is not provided:
-    the one divergence in defaults).  ``"tumap"`` is a = b = 1; ``"umap"`` fits them (:func:`find_ab_params`) unless both are given.
+    set_op_mix_ratio=1, local_connectivity=1, init="pca"`` (:func:`umap_init`, or ``"normlaplacian"``: the Laplacian eigenvectors
+    of the graph through :func:`umap`; uwot's default ``"spectral"`` is provided by ``gficf_amd.umap(..., init="spectral")`` and
+    :func:`spectral_init`, and still raises here: the default stays ``"pca"``, the one divergence in defaults).  ``"tumap"`` is a = b = 1; ``"umap"`` fits them (:func:`find_ab_params`) unless both are given.
 
     ``data["embedded"]`` becomes a pandas DataFrame with the columns ``X`` and ``Y`` (what ``clustcells(from_embedded=True)``
     searches), ``data["reduction"]`` the name, and with ``ret_model_pred`` ``data["uwot"]`` the dict of :func:`umap`.  Not provided,
@@ -1319,7 +1492,7 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
         raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
     cells = np.asarray(data["pca"]["cells"], dtype=np.float64)
     N = cells.shape[0]
-    Y0 = umap_init(o["init"], cells, N, seed)
+    Y0 = "normlaplacian" if isinstance(o["init"], str) and o["init"] == "normlaplacian" else umap_init(o["init"], cells, N, seed)
     if reduction == "tumap":
         a = b = 1.0
     elif o["a"] is not None and o["b"] is not None:
@@ -2372,6 +2545,40 @@ class HipOps:
         from . import _umap_lib
 
         check(_umap_lib.load().gficf_umap_sync(self._bind(), _tptr(ws)))
+
+    # -- spectral start (libgficf_spectral.so)
+    @staticmethod
+    def graph_components_workspace_bytes(N: int) -> int:
+        """Device scratch of ``graph_components`` (libgficf_spectral.so)."""
+        from . import _spectral_lib
+
+        return int(_spectral_lib.load().gficf_graph_components_workspace_bytes(int(N)))
+
+    def graph_components(self, N, rowptr, col, capacity, labels, info, ws):
+        """The connected components of a CSR graph (rowptr int64 N + 1, col int32, ``capacity`` entries that may be read): labels int32
+        N (the smallest vertex id of each vertex's component), info int64 (2) = {components, rounds}.  Synchronises once per round; a
+        bad row pointer or column is raised here."""
+        from . import _spectral_lib
+
+        check(_spectral_lib.load().gficf_graph_components_device(self._bind(), int(N), _tptr(rowptr), _tptr(col), int(capacity), _tptr(labels),
+                                                                 _tptr(info), _tptr(ws), int(ws.numel() * ws.element_size())))
+
+    @staticmethod
+    def spectral_workspace_bytes(N: int, capacity: int, ndim: int, m: int = 32) -> int:
+        from . import _spectral_lib
+
+        return int(_spectral_lib.load().gficf_spectral_workspace_bytes(int(N), int(capacity), int(ndim), int(m)))
+
+    def spectral(self, N, rowptr, col, val, capacity, ndim, start, tol, m, max_restarts, ws, theta, resid, vectors, info):
+        """The ndim leading eigenpairs of S = D^-1/2 P D^-1/2 beside its trivial one (include/gficf_spectral.h): start and vectors (N,
+        ndim) float64, theta / resid float64 (ndim), info int64 (4) = {components, restarts, multiplications, converged}.  With more
+        than one component theta, resid and vectors are left untouched.  Synchronises once per restart cycle."""
+        from . import _spectral_lib
+
+        check(_spectral_lib.load().gficf_spectral_device(self._bind(), int(N), _tptr(rowptr), _tptr(col), _tptr(val), int(capacity), int(ndim),
+                                                         _tptr(start), float(tol), int(m), int(max_restarts), _tptr(ws),
+                                                         int(ws.numel() * ws.element_size()), _tptr(theta), _tptr(resid), _tptr(vectors),
+                                                         _tptr(info)))
 
     # -- t-SNE (libgficf_tsne.so)
     @staticmethod
