@@ -922,6 +922,78 @@ class ClusterLabels(np.ndarray):
     n_edges = 0
 
 
+
+def _leiden_matrix(A, resolution):
+    """The checks of ``leiden`` / ``leiden_refine`` that need no device, and the matrix as the C ABI takes it."""
+    import scipy.sparse as sp
+
+    if not (np.isfinite(resolution) and resolution >= 0.0):
+        raise ValueError("resolution must be finite and not negative")
+    A = sp.csc_matrix(A)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("the adjacency matrix must be square")
+    if not A.has_sorted_indices:
+        A = A.copy()
+        A.sort_indices()
+    return (A.shape[0], np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32),
+            np.ascontiguousarray(A.data, dtype=np.float64))
+
+
+def _leiden_labels(labels, N, what):
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if lab.shape != (N,):
+        raise ValueError(f"{what} must hold one label per vertex ({N}), not {lab.shape}")
+    if N and (lab.min() < 0 or lab.max() >= N):
+        raise ValueError(f"{what} labels must lie in [0, {N})")
+    return lab
+
+
+def leiden(A, resolution: float = 1.0, n_iterations: int = 2, seed: int = 0, init=None, ctx: Context | None = None):
+    """Leiden community detection (Traag, Waltman, van Eck 2019) on a symmetric weighted adjacency matrix, what
+    ``clustcells(community.algo = "leiden")`` of the reference runs (R/clustCells.R:100-107,
+    ``leiden::leiden(object = g, resolution_parameter = resolution)``).
+
+    RELAXED CONTRACT (include/gficf_leiden.h): the algorithm and its objective are Leiden's — the modularity of
+    :func:`run_modularity_clustering` with a resolution, local moving, refinement into well-connected sub-communities,
+    aggregation by the refined partition — the visiting order and the random bits are not leidenalg's; the refinement takes
+    the target of largest gain where leidenalg draws one at random.  Every community returned is connected.  The result is
+    a function of the arguments, bit for bit.  ``init``: a start partition (labels in [0, N)); ``n_iterations`` >= 1:
+    each further iteration resumes from the last one's result.
+
+    Returns ``ClusterLabels`` (int32, 0-based, clusters numbered by decreasing size) with ``.modularity`` and ``.n_clusters``.
+    """
+    from . import _leiden_lib
+
+    if n_iterations < 1:
+        raise ValueError("n_iterations must be at least 1")
+    N, indptr, indices, x = _leiden_matrix(A, resolution)
+    start = None if init is None else _leiden_labels(init, N, "init")
+    labels = np.zeros(max(N, 1), dtype=np.int32)
+    nc, q = ctypes.c_int64(0), ctypes.c_double(0.0)
+    ctx = ctx or default_context()
+    check(_leiden_lib.load().gficf_leiden_host(ctx.handle, N, _np_ptr(indptr), _np_ptr(indices), _np_ptr(x), len(indices), float(resolution),
+                                               int(n_iterations), int(seed) & 0x7FFFFFFF, None if start is None else _np_ptr(start),
+                                               _np_ptr(labels), ctypes.byref(nc), ctypes.byref(q)))
+    out = labels[:N].view(ClusterLabels)
+    out.modularity, out.n_clusters = q.value, nc.value
+    return out
+
+
+def leiden_refine(A, labels, resolution: float = 1.0, ctx: Context | None = None):
+    """The refinement stage of :func:`leiden` alone: every community of ``labels`` split into connected, well-connected
+    sub-communities (include/gficf_leiden.h).  Returns int32[N]: the smallest member id of every vertex's refined community."""
+    from . import _leiden_lib
+
+    N, indptr, indices, x = _leiden_matrix(A, resolution)
+    lab = _leiden_labels(labels, N, "labels")
+    out = np.zeros(max(N, 1), dtype=np.int32)
+    nr = ctypes.c_int64(0)
+    ctx = ctx or default_context()
+    check(_leiden_lib.load().gficf_leiden_refine_host(ctx.handle, N, _np_ptr(indptr), _np_ptr(indices), _np_ptr(x), len(indices), float(resolution),
+                                                      _np_ptr(lab), _np_ptr(out), ctypes.byref(nr)))
+    return out[:N]
+
+
 def transpose_gficf(gficf_mat, ctx: Context | None = None):
     """``data$pca$cells = t(data$gficf)`` (reference R/dimensinalityReduction.R:33, :100): the genes x cells CSC
     matrix as a cells x genes CSC matrix (cell indices ascending within every gene, every stored entry kept)."""
@@ -2018,7 +2090,7 @@ def phenograph(X, k: int = 15, dist_method: str = "manhattan", resolution: float
     return out
 
 
-COMMUNITY_ALGOS = ("louvian", "louvian 2", "louvian 3")
+COMMUNITY_ALGOS = ("louvian", "louvian 2", "louvian 3", "leiden")
 
 
 def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method: str = "manhattan", nt: int = 2,
@@ -2031,15 +2103,16 @@ def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method
 
     ``data``: dict with ``"pca": {"cells": N x d}`` (or ``"embedded"``: N x >=2 array when ``from_embedded``) and
     ``"gficf"`` (genes x cells CSC).  ``community_algo``: "louvian 2" / "louvian 3" (resolution, n_iter as given) or
-    "louvian" (the reference calls igraph::cluster_louvain there: plain modularity, i.e. resolution 1); the igraph /
-    leidenalg algorithms ("walktrap", "fastgreedy", "leiden") are third-party and not provided.  ``nt`` is accepted for
+    "louvian" (the reference calls igraph::cluster_louvain there: plain modularity, i.e. resolution 1) or "leiden"
+    (:100-107: :func:`leiden` with ``resolution``, two iterations and ``seed``; relaxed contract of include/gficf_leiden.h);
+    the igraph algorithms "walktrap" and "fastgreedy" are third-party and not provided.  ``nt`` is accepted for
     signature compatibility (no CPU threads); ``seed`` and ``n_start`` act as in ``run_modularity_clustering``.  Returns ``data`` updated with ``community``
     (1-based like the reference), ``cluster`` (the labels as strings, ``data$embedded$cluster``), ``cluster.gene.rnk``
     (+ its column labels ``cluster.labels``) and, with ``store_graph``, ``cell.graph`` (the edge columns) and
     ``cell.adjacency``.
     """
     if community_algo not in COMMUNITY_ALGOS:
-        raise ValueError(f"community_algo must be one of {COMMUNITY_ALGOS} (igraph / leidenalg algorithms are not provided)")
+        raise ValueError(f"community_algo must be one of {COMMUNITY_ALGOS} (the igraph algorithms \"walktrap\" and \"fastgreedy\" are not provided)")
     if from_embedded:
         if data.get("embedded") is None:
             raise ValueError("First run runReduction to embed your cells")
@@ -2050,7 +2123,11 @@ def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method
         X = np.asarray(data["pca"]["cells"])
     N = X.shape[0]
     lv = (1.0, 1, 1, n_iter, 0) if community_algo == "louvian" else (resolution, 1 if community_algo == "louvian 2" else 2, n_start, n_iter, seed)
-    if store_graph:
+    if community_algo == "leiden":                            # the staged path either way: the fused entry is Louvain's
+        edges = clustcells_graph(X, k, dist_method, verbose, ctx)
+        A = jaccard_adjacency(edges, N, ctx)
+        community = leiden(A, resolution, 2, seed, None, ctx)
+    elif store_graph:
         edges = clustcells_graph(X, k, dist_method, verbose, ctx)
         A = jaccard_adjacency(edges, N, ctx)
         community = run_modularity_clustering(A, 1, lv[0], lv[1], lv[2], lv[3], lv[4], verbose and community_algo != "louvian", ctx)
@@ -2713,6 +2790,33 @@ class HipOps:
                                           ctypes.byref(q),
                                           _tptr(ws), int(ws.numel() * ws.element_size())))
         return nc.value, q.value
+
+    def leiden_workspace_bytes(self, N: int, nnz: int) -> int:
+        """Device scratch of ``leiden`` and ``leiden_refine``."""
+        from . import _leiden_lib
+
+        return int(_leiden_lib.load().gficf_leiden_workspace_bytes(int(N), int(nnz)))
+
+    def leiden(self, N, indptr, indices, x, resolution, n_iterations, labels, ws, seed: int = 0, init=None):
+        """Leiden on a device-resident symmetric adjacency matrix (indptr int64, indices int32, x float64); init: int32[N] or None.
+        Returns (n_clusters, modularity); labels: int32[N]."""
+        from . import _leiden_lib
+
+        nc, q = ctypes.c_int64(0), ctypes.c_double(0.0)
+        check(_leiden_lib.load().gficf_leiden_device(self._bind(), int(N), _tptr(indptr), _tptr(indices), _tptr(x), int(indices.numel()),
+                                                     float(resolution), int(n_iterations), int(seed), _tptr(init), _tptr(labels), ctypes.byref(nc),
+                                                     ctypes.byref(q), _tptr(ws), int(ws.numel() * ws.element_size())))
+        return nc.value, q.value
+
+    def leiden_refine(self, N, indptr, indices, x, resolution, labels_in, refined, ws):
+        """The refinement stage alone; refined: int32[N], the smallest member id of every vertex's refined community.  Returns their number."""
+        from . import _leiden_lib
+
+        nr = ctypes.c_int64(0)
+        check(_leiden_lib.load().gficf_leiden_refine_device(self._bind(), int(N), _tptr(indptr), _tptr(indices), _tptr(x), int(indices.numel()),
+                                                            float(resolution), _tptr(labels_in), _tptr(refined), ctypes.byref(nr), _tptr(ws),
+                                                            int(ws.numel() * ws.element_size())))
+        return nr.value
 
     def csc_transpose_workspace_bytes(self, G: int, n_cells: int) -> int:
         return int(self.L.gficf_csc_transpose_workspace_bytes(int(G), int(n_cells)))
