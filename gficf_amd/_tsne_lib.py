@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from . import _lib
+from . import _addon, _lib
 
 LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libgficf_tsne.so")
 ABI_VERSION = 1
@@ -29,22 +29,4 @@ SIGNATURES = {
     "gficf_tsne_host": (_int, [_vp, _vp, _i64, _int, _i64, _d, _int, _int, _int, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
-_lib_p = None
-
-
-def load() -> ctypes.CDLL:
-    """Load libgficf_tsne.so (after libgficf_hip.so, whose copy it then shares); raises if it has not been built."""
-    global _lib_p
-    if _lib_p is None:
-        _lib.load()
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `make -C gficf_amd/csrc` (hipcc, --offload-arch=gfx950)")
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        if L.gficf_tsne_abi_version() != ABI_VERSION:
-            raise ImportError(f"{LIB_PATH}: ABI {L.gficf_tsne_abi_version()}, expected {ABI_VERSION}")
-        _lib_p = L
-    return _lib_p
+load = _addon.loader(globals(), "gficf_tsne_abi_version")

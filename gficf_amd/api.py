@@ -1291,24 +1291,15 @@ def umap_layout(P, init, n_epochs: int, a: float = 1.0, b: float = 1.0, learning
     taken as CSR with sorted columns) from the coordinates ``init`` (N x 2): ``gficf_umap_layout_device``, the integer schedule
     and the owner-computes update of include/gficf_umap.h.  Returns the N x 2 float32 coordinates; running ``[0, a)`` and then
     ``[a, n)`` from its result gives the bits of ``[0, n)``."""
-    import scipy.sparse as sp
-
-    P = sp.csr_matrix(P)
-    if P.shape[0] != P.shape[1]:
-        raise ValueError("P must be square")
-    if not P.has_sorted_indices:
-        P = P.sorted_indices()
-    N = P.shape[0]
+    csr = _square_csr(P)
+    N = csr[0]
     Y = np.ascontiguousarray(init, dtype=np.float32)
     if Y.shape != (N, 2):
         raise ValueError(f"init must be an N x 2 = {N} x 2 array")
     epoch_end = int(n_epochs) if epoch_end is None else int(epoch_end)
     ops = _umap_hip(device)
     tc, dev = ops.torch, f"cuda:{device}"
-    cap = int(P.nnz)
-    rowptr = tc.from_numpy(P.indptr.astype(np.int64)).to(dev)
-    col = tc.from_numpy(np.ascontiguousarray(P.indices, dtype=np.int32)).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
-    val = tc.from_numpy(np.ascontiguousarray(P.data, dtype=np.float32)).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
+    _, cap, rowptr, col, val = _dev_csr(ops, csr, device)
     d_Y = tc.from_numpy(Y).to(dev)
     ws = tc.empty(max(ops.umap_layout_workspace_bytes(N, cap), 1), dtype=tc.uint8, device=dev)
     ops.umap_layout(N, rowptr, col, val, cap, a, b, repulsion_strength, learning_rate, negative_sample_rate, n_epochs, epoch_begin, epoch_end, seed,
@@ -1317,27 +1308,41 @@ def umap_layout(P, init, n_epochs: int, a: float = 1.0, b: float = 1.0, learning
     return d_Y.cpu().numpy()
 
 
-def _spectral_csr(P):
-    """P as square scipy CSR with sorted columns."""
+def _square_csr(P, allow_arrays: bool = False):
+    """``(N, indptr int64, indices int32, data float32)`` of the graph ``P``: a square scipy sparse matrix, taken as CSR with
+    sorted columns; with ``allow_arrays`` also the three arrays themselves as ``(indptr, indices, data)``, which are handed to
+    the library unchecked."""
     import scipy.sparse as sp
 
+    if allow_arrays and isinstance(P, tuple):
+        indptr, indices, data = P
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        return len(indptr) - 1, indptr, np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(data, dtype=np.float32)
     P = sp.csr_matrix(P)
     if P.shape[0] != P.shape[1]:
         raise ValueError("P must be square")
-    if P.shape[0] < 1:
-        raise ValueError("P has no vertices")
     if not P.has_sorted_indices:
         P = P.sorted_indices()
-    return P
+    return P.shape[0], P.indptr.astype(np.int64), np.ascontiguousarray(P.indices, dtype=np.int32), np.ascontiguousarray(P.data, dtype=np.float32)
 
 
-def _spectral_dev_csr(ops, P, device):
+def _dev_csr(ops, csr, device):
+    """What :func:`_square_csr` returned, on the device: ``(N, cap, rowptr, col, val)``; an empty graph gets 1-element
+    placeholders, so every pointer handed to the library is valid."""
     tc, dev = ops.torch, f"cuda:{device}"
-    cap = int(P.nnz)
-    rowptr = tc.from_numpy(P.indptr.astype(np.int64)).to(dev)
-    col = tc.from_numpy(np.ascontiguousarray(P.indices, dtype=np.int32)).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
-    val = tc.from_numpy(np.ascontiguousarray(P.data, dtype=np.float32)).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
-    return rowptr, col, val, cap
+    N, indptr, indices, data = csr
+    cap = int(len(indices))
+    rowptr = tc.from_numpy(indptr).to(dev)
+    col = tc.from_numpy(indices).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
+    val = tc.from_numpy(data).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
+    return N, cap, rowptr, col, val
+
+
+def _spectral_csr(P):
+    csr = _square_csr(P)
+    if csr[0] < 1:
+        raise ValueError("P has no vertices")
+    return csr
 
 
 def graph_components(P, ret_rounds: bool = False, device: int = 0):
@@ -1345,11 +1350,10 @@ def graph_components(P, ret_rounds: bool = False, device: int = 0):
     stored): ``gficf_graph_components_device`` (include/gficf_spectral.h), hook and pointer-jump on the device.  Returns
     ``(labels, n)``: ``labels[i]`` (int32) is the smallest vertex id of i's component, ``n`` the number of components; with
     ``ret_rounds`` also the number of rounds it took."""
-    P = _spectral_csr(P)
-    N = P.shape[0]
+    csr = _spectral_csr(P)
     ops = _umap_hip(device)
     tc, dev = ops.torch, f"cuda:{device}"
-    rowptr, col, _, cap = _spectral_dev_csr(ops, P, device)
+    N, cap, rowptr, col, _ = _dev_csr(ops, csr, device)
     labels = tc.empty(N, dtype=tc.int32, device=dev)
     info = tc.zeros(2, dtype=tc.int64, device=dev)
     ws = tc.empty(max(ops.graph_components_workspace_bytes(N), 1), dtype=tc.uint8, device=dev)
@@ -1386,14 +1390,14 @@ def _spectral_args(N: int, ndim, m, tol, max_restarts, start):
 
 def _spectral_solve(P, ndim=2, start=None, seed=18051982, tol=1e-4, m=32, max_restarts=200, device: int = 0) -> dict:
     """:func:`spectral_embedding` without its verdicts: a disconnected graph comes back with ``vectors`` None."""
-    P = _spectral_csr(P)
-    N = P.shape[0]
+    csr = _spectral_csr(P)
+    N = csr[0]
     ndim, m, max_restarts, start = _spectral_args(N, ndim, m, tol, max_restarts, start)
     if start is None:
         start = np.random.default_rng(seed).standard_normal((N, ndim))
     ops = _umap_hip(device)
     tc, dev = ops.torch, f"cuda:{device}"
-    rowptr, col, val, cap = _spectral_dev_csr(ops, P, device)
+    _, cap, rowptr, col, val = _dev_csr(ops, csr, device)
     d_start = tc.from_numpy(start).to(dev)
     theta = tc.full((ndim,), float("nan"), dtype=tc.float64, device=dev)
     resid = tc.full((ndim,), float("nan"), dtype=tc.float64, device=dev)
@@ -1444,11 +1448,11 @@ def spectral_init(P, seed: int = 18051982, jitter: bool = True, device: int = 0,
     :func:`spectral_embedding`; with ``jitter`` (uwot's ``"spectral"``) scaled to a largest magnitude of 10 plus N(0, 1e-4) noise,
     the scaling of :func:`umap_init`'s ``"pca"``; without (uwot's ``"normlaplacian"``) the raw unit vectors.  One
     ``default_rng(seed)`` draws the start block first and the noise second.  ``solver_kw``: ``tol``, ``m``, ``max_restarts``."""
-    P = _spectral_csr(P)
+    N = _spectral_csr(P)[0]
     rng = np.random.default_rng(seed)
-    if P.shape[0] <= 2:
-        raise ValueError(f"N = {P.shape[0]} vertices for ndim = 2: N must exceed ndim")
-    start = rng.standard_normal((P.shape[0], 2))
+    if N <= 2:
+        raise ValueError(f"N = {N} vertices for ndim = 2: N must exceed ndim")
+    start = rng.standard_normal((N, 2))
     r = spectral_embedding(P, 2, start=start, device=device, **solver_kw)
     return _spectral_coordinates(r["vectors"], rng, jitter)
 
@@ -1604,33 +1608,11 @@ def _tsne_k(perplexity, N: int) -> int:
     return K + 1
 
 
-def _tsne_csr(P):
-    """(N, indptr int64, indices int32, data float32) of ``P``: a scipy sparse matrix (taken as CSR with sorted columns), or the
-    three arrays themselves as ``(indptr, indices, data)``, which are handed to the library unchecked."""
-    import scipy.sparse as sp
-
-    if isinstance(P, tuple):
-        indptr, indices, data = P
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        return len(indptr) - 1, indptr, np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(data, dtype=np.float32)
-    P = sp.csr_matrix(P)
-    if P.shape[0] != P.shape[1]:
-        raise ValueError("P must be square")
-    if not P.has_sorted_indices:
-        P = P.sorted_indices()
-    return P.shape[0], P.indptr.astype(np.int64), np.ascontiguousarray(P.indices, dtype=np.int32), np.ascontiguousarray(P.data, dtype=np.float32)
-
-
 def _tsne_dev_csr(ops, P):
-    tc, dev = ops.torch, f"cuda:{ops.device}"
-    N, indptr, indices, data = _tsne_csr(P)
-    cap = int(len(indices))
-    if N < 1 or len(data) != cap:
+    csr = _square_csr(P, allow_arrays=True)
+    if csr[0] < 1 or len(csr[3]) != len(csr[2]):
         raise ValueError("P needs at least one row, and as many values as columns")
-    rowptr = tc.from_numpy(indptr).to(dev)
-    col = tc.from_numpy(indices).to(dev) if cap else tc.empty(1, dtype=tc.int32, device=dev)
-    val = tc.from_numpy(data).to(dev) if cap else tc.empty(1, dtype=tc.float32, device=dev)
-    return N, cap, rowptr, col, val
+    return _dev_csr(ops, csr, ops.device)
 
 
 def _tsne_state(a, N: int, name: str, fill: float) -> np.ndarray:

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_gsea.h"
 
@@ -385,11 +386,8 @@ int gficf_gsea_device(gficf_ctx* ctx, int64_t G, int32_t C, const double* d_stat
 }
 
 int gficf_gsea_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & GS_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "the statistics hold a NaN or an infinite value");
   if (st & GS_ST_RANGE) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "a pathway member outside [0, G)");

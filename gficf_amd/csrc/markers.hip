@@ -19,6 +19,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_markers.h"
 
@@ -483,11 +484,8 @@ int gficf_cluster_markers_device(gficf_ctx* ctx, int64_t G, int64_t N, const int
 }
 
 int gficf_cluster_markers_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & MK_ST_LABEL) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "a cluster label outside [0, C)");
   if (st & MK_ST_EMPTY) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "a cluster without cells");

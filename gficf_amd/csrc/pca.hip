@@ -22,6 +22,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_pca.h"
 
@@ -824,11 +825,8 @@ int gficf_rsvd_device(gficf_ctx* ctx, int64_t G, int64_t N, const int64_t* d_col
 }
 
 int gficf_rsvd_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & PCA_ST_CSC) GFICF_FAIL(GFICF_ERR_BAD_CSC, "a row index out of range or a bad column pointer");
   if (st & PCA_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "a NaN or an infinite value in the matrix or in a dense operand");

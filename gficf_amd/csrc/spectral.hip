@@ -20,6 +20,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_spectral.h"
 
@@ -30,9 +31,9 @@ constexpr int SP_HUB_LEN = 256;              // a row longer than this is multip
 constexpr int SP_GROUP = 8;                  // lanes per row otherwise
 constexpr int SP_HUB_WAVES = 1024;           // waves that share the hub list, at most
 constexpr int SP_MAXB = GFICF_SPECTRAL_MAX_NDIM;
-constexpr uint32_t SP_ST_ID = 1u;            // a column outside [0, N)
-constexpr uint32_t SP_ST_VALUE = 2u;         // a value of P that is not positive and finite
-constexpr uint32_t SP_ST_CSC = 4u;           // a row pointer that does not start at 0, decreases or leaves [0, capacity]
+constexpr uint32_t SP_ST_ID = GFICF_AST_ID;          // a column outside [0, N)
+constexpr uint32_t SP_ST_VALUE = GFICF_AST_VALUE;    // a value of P that is not positive and finite
+constexpr uint32_t SP_ST_CSC = GFICF_AST_CSC;        // a row pointer that does not start at 0, decreases or leaves [0, capacity]
 
 unsigned sp_grid(int64_t n) { return (unsigned)gficf_ceil_div(n > 0 ? n : 1, 256); }
 

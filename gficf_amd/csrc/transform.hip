@@ -7,8 +7,8 @@
 //   search    k_tr_tiles, k_tr_merge   (transform_search.h) the M x k table over all N training rows
 //   weights   k_tr_smooth      one lane per new cell: rho, the bisection for sigma, the row-local floor, the k memberships; bad ids
 //                              and non-finite distances flagged
-//   init      k_tr_finite, k_tr_init   the trained plane checked; one lane per new cell: the weighted mean of its k heads
-//   layout    k_tr_finite, k_tr_layout   ONE launch for the whole epoch range.  A group of 8 lanes per new cell.  The trained
+//   init      k_addon_finite, k_tr_init   the trained plane checked; one lane per new cell: the weighted mean of its k heads
+//   layout    k_addon_finite, k_tr_layout   ONE launch for the whole epoch range.  A group of 8 lanes per new cell.  The trained
 //                              cells do not move, so the group reads its row once: the k schedule words and the k head
 //                              positions go to LDS and stay there for every epoch; the running position stays in registers;
 //                              per due entry the lanes fetch the negative samples side by side before the attraction is
@@ -20,28 +20,22 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_kernels.h"
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_transform.h"
 #include "transform_search.h"
+#include "umap_force.h"
 
 namespace {
 
 constexpr int TR_GROUP = 8;                  // lanes per new cell in the layout
 constexpr int TR_LAY_THREADS = 64;           // one wave = 8 cells per workgroup: few cells still spread over many CUs
 constexpr int TR_VOTE_THREADS = 64;
-constexpr uint32_t TR_ST_ID = 1u;            // a neighbour id outside [1, N], a label outside [0, C)
-constexpr uint32_t TR_ST_VALUE = 2u;         // a non-finite distance, membership or coordinate
+constexpr uint32_t TR_ST_ID = GFICF_AST_ID;          // a neighbour id outside [1, N], a label outside [0, C)
+constexpr uint32_t TR_ST_VALUE = GFICF_AST_VALUE;    // a non-finite distance, membership or coordinate
 
 unsigned tr_grid(int64_t n, int per = 256) { return (unsigned)gficf_ceil_div(n > 0 ? n : 1, per); }
-
-__device__ inline float tr_dist(float d) { return fmaxf(d, 0.f); }      // cosine / correlation can round a hair below 0
-
-__device__ inline u64 tr_mix(u64 z) {         // the splitmix64 finaliser
-  z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-  z ^= z >> 27; z *= 0x94d049bb133111ebull;
-  z ^= z >> 31;
-  return z;
-}
 
 // ------------------------------------------------------------------------------------------------ memberships
 __global__ __launch_bounds__(256) void k_tr_smooth(const int32_t* __restrict__ idx, const float* __restrict__ dist, int64_t N, int64_t M, int k,
@@ -55,7 +49,7 @@ __global__ __launch_bounds__(256) void k_tr_smooth(const int32_t* __restrict__ i
   for (int c = 0; c < k; ++c) {
     const float raw = dist[(int64_t)c * ld + i];
     bad_v |= !isfinite(raw);
-    const float d = tr_dist(raw);
+    const float d = uf_dist(raw);
     rowsum += d;
     if (d > 0.f) {
       ++cnt;
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(256) void k_tr_smooth(const int32_t* __restrict__ i
   for (int it = 0; it < 64; ++it) {
     float psum = 0.f;
     for (int c = 0; c < k; ++c) {
-      const float x = tr_dist(dist[(int64_t)c * ld + i]) - rho;
+      const float x = uf_dist(dist[(int64_t)c * ld + i]) - rho;
       psum += x > 0.f ? expf(-x / mid) : 1.f;
     }
     if (fabsf(psum - target) < 1e-5f) break;
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void k_tr_smooth(const int32_t* __restrict__ i
   bool bad_id = false;
   for (int c = 0; c < k; ++c) {
     const int32_t j = idx[(int64_t)c * ld + i];
-    const float x = tr_dist(dist[(int64_t)c * ld + i]) - rho;
+    const float x = uf_dist(dist[(int64_t)c * ld + i]) - rho;
     float w;
     if (j < 1 || (int64_t)j > N) {
       bad_id = true;
@@ -114,12 +108,6 @@ __global__ __launch_bounds__(256) void k_tr_smooth(const int32_t* __restrict__ i
 }
 
 // ------------------------------------------------------------------------------------------------ initial position
-__global__ __launch_bounds__(256) void k_tr_finite(const float* __restrict__ Y, int64_t n, uint32_t* __restrict__ status) {
-  bool bad = false;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) bad |= !isfinite(Y[t]);
-  if (bad) atomicOr(status, TR_ST_VALUE);
-}
-
 __global__ __launch_bounds__(256) void k_tr_init(const int32_t* __restrict__ idx, int64_t ld, const float* __restrict__ W, int64_t ld_w,
                                                  const float2* __restrict__ Yt, int64_t N, int64_t M, int k, float2* __restrict__ Y,
                                                  uint32_t* __restrict__ status) {
@@ -159,43 +147,6 @@ struct TrLay {
   float2* Y;
   uint32_t* status;
 };
-
-__device__ inline float tr_clip(float x) { return fminf(fmaxf(x, -4.f), 4.f); }
-
-template <bool T1>
-__device__ inline void tr_attract(float& yx, float& yy, float jx, float jy, float alpha, const TrLay& L) {
-  const float dx = yx - jx, dy = yy - jy, d2 = dx * dx + dy * dy;
-  float coef = 0.f;
-  if (d2 > 0.f) {
-    if (T1) {
-      coef = -2.f / (d2 + 1.f);
-    } else {
-      const float pd = powf(d2, L.b);
-      coef = (L.m2ab * pd) / (d2 * (L.a * pd + 1.f));
-    }
-  }
-  yx += alpha * tr_clip(coef * dx);
-  yy += alpha * tr_clip(coef * dy);
-}
-
-template <bool T1>
-__device__ inline void tr_repulse(float& yx, float& yy, float jx, float jy, float alpha, const TrLay& L) {
-  const float dx = yx - jx, dy = yy - jy, d2 = dx * dx + dy * dy;
-  float sx = 4.f, sy = 4.f;
-  if (d2 > 0.f) {
-    float coef;
-    if (T1) {
-      coef = L.g2b / ((0.001f + d2) * (d2 + 1.f));
-    } else {
-      const float pd = powf(d2, L.b);
-      coef = L.g2b / ((0.001f + d2) * (L.a * pd + 1.f));
-    }
-    sx = tr_clip(coef * dx);
-    sy = tr_clip(coef * dy);
-  }
-  yx += alpha * sx;
-  yy += alpha * sy;
-}
 
 // LDS per workgroup: [8 cells][k] head positions (float2), then [8 cells][k] schedule words
 size_t tr_layout_lds(int k) { return (size_t)(TR_LAY_THREADS / TR_GROUP) * (size_t)k * (sizeof(float2) + sizeof(uint32_t)); }
@@ -248,7 +199,7 @@ __global__ __launch_bounds__(TR_LAY_THREADS) void k_tr_layout(const TrLay L) {
   const u64 e0 = (L.qoff + (u64)i) * (u64)k;
   for (int n = L.eb; n < L.ee; ++n) {
     const float alpha = L.lr * (1.f - (float)n / (float)L.n_epochs);
-    const u64 kn = tr_mix(L.seed + (u64)n), un = (u64)n;
+    const u64 kn = uf_mix(L.seed + (u64)n), un = (u64)n;
     for (int base = 0; base < k; base += G) {
       const int c = base + lane;
       bool due = false;
@@ -260,19 +211,19 @@ __global__ __launch_bounds__(TR_LAY_THREADS) void k_tr_layout(const TrLay L) {
       while (mask) {                                              // the same in every lane of the group
         const int t = __builtin_ctzll(mask);
         mask &= mask - 1ull;
-        const u64 ke = tr_mix(kn + e0 + (u64)(base + t));
+        const u64 ke = uf_mix(kn + e0 + (u64)(base + t));
         const float2 yj = sY[base + t];                           // one address for the group: a broadcast read
         for (int s0 = 0;; s0 += G) {                              // the first round also applies the attraction
           float2 yn = make_float2(0.f, 0.f);
           if (s0 + lane < L.rate) {
-            const u64 key = tr_mix(ke + (u64)(s0 + lane));
+            const u64 key = uf_mix(ke + (u64)(s0 + lane));
             yn = L.Yt[((key >> 32) * (u64)L.N) >> 32];
           }
-          if (s0 == 0) tr_attract<T1>(yx, yy, yj.x, yj.y, alpha, L);
+          if (s0 == 0) uf_attract<T1>(yx, yy, yj.x, yj.y, alpha, L);
           const int cnt = L.rate - s0 < G ? L.rate - s0 : G;
           for (int u = 0; u < cnt; ++u) {
             const float nx = __shfl(yn.x, u, G), ny = __shfl(yn.y, u, G);
-            tr_repulse<T1>(yx, yy, nx, ny, alpha, L);
+            uf_repulse<T1>(yx, yy, nx, ny, alpha, L);
           }
           if (s0 + G >= L.rate) break;
         }
@@ -319,12 +270,6 @@ __global__ __launch_bounds__(256) void k_tr_in(const double* __restrict__ in, in
   const double x = in[(t & 1) * n + (t >> 1)];
   if (!isfinite(x)) atomicOr(status, TR_ST_VALUE);
   Y[t] = (float)x;
-}
-
-__global__ __launch_bounds__(256) void k_tr_out(const float* __restrict__ Y, int64_t n, double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2 * n) return;
-  out[(t & 1) * n + (t >> 1)] = (double)Y[t];
 }
 
 // ------------------------------------------------------------------------------------------------ checks and stage bodies
@@ -406,7 +351,7 @@ int tr_weights(gficf_ctx* ctx, uint32_t* status, const int32_t* d_idx, const flo
 }
 
 int tr_plane_finite(gficf_ctx* ctx, uint32_t* status, const float* d_Y_train, int64_t N) {
-  hipLaunchKernelGGL(k_tr_finite, dim3(tr_grid(2 * N) < 1024 ? tr_grid(2 * N) : 1024), dim3(256), 0, ctx->stream, d_Y_train, 2 * N, status);
+  hipLaunchKernelGGL(k_addon_finite, dim3(tr_grid(2 * N) < 1024 ? tr_grid(2 * N) : 1024), dim3(256), 0, ctx->stream, d_Y_train, 2 * N, status);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
 }
@@ -555,11 +500,8 @@ int gficf_transform_vote_device(gficf_ctx* ctx, const int32_t* d_idx, int64_t ld
 }
 
 int gficf_transform_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & TR_ST_ID) GFICF_FAIL(GFICF_ERR_BAD_ID, "a neighbour id outside [1, N] or a label outside [0, C)");
   if (st & TR_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "a non-finite distance, membership or coordinate");
@@ -686,14 +628,14 @@ int gficf_transform_host(gficf_ctx* ctx, const double* X_train, int64_t N, int64
       if (init) hipLaunchKernelGGL(k_tr_in, dim3(tr_grid(2 * M)), dim3(256), 0, st, (const double*)d_init, M, d_Y, status);
       else rc = tr_init(ctx, status, h.d_idx, ld, d_w, ld, d_Yt, N, M, k, d_Y);
       if (!rc && y0) {
-        hipLaunchKernelGGL(k_tr_out, dim3(tr_grid(2 * M)), dim3(256), 0, st, (const float*)d_Y, M, d_y0);
+        hipLaunchKernelGGL(k_addon_out, dim3(tr_grid(2 * M)), dim3(256), 0, st, (const float*)d_Y, M, d_y0);
         io.down(y0, d_y0, sizeof(double) * 2 * (size_t)M);
       }
       if (!rc)
         rc = tr_layout(ctx, status, h.d_idx, ld, d_w, ld, d_Yt, N, M, k, (float)a, (float)b, (float)gamma, (float)learning_rate,
                        negative_sample_rate, n_epochs, epoch_begin, epoch_end, seed, query_offset, d_Y);
       if (!rc) {
-        hipLaunchKernelGGL(k_tr_out, dim3(tr_grid(2 * M)), dim3(256), 0, st, (const float*)d_Y, M, d_emb);
+        hipLaunchKernelGGL(k_addon_out, dim3(tr_grid(2 * M)), dim3(256), 0, st, (const float*)d_Y, M, d_emb);
         if (io.ok()) io.e = hipGetLastError();
         io.down(embedding, d_emb, sizeof(double) * 2 * (size_t)M);
         if (idx) io.down(idx, h.d_idx, sizeof(int32_t) * mk);

@@ -5,9 +5,7 @@
 //
 // Launches of the affinity stage (N points, K = k - 1 columns, M = 2 N K items: every conditional once as (i, j), once as (j, i)):
 //   k_ts_beta        one lane per point: the bisection for beta in f64, the K conditionals; bad ids and distances flagged
-//   k_ts_key_col, (sort), k_ts_key_row, (sort)   the items sorted by (row, column) with the library's stable radix passes
-//   k_ts_heads       one lane per sorted item: the first of a (row, column) pair combines with its mirror, if that follows it
-//   (scan), k_ts_emit   positions of the kept entries; columns, values, row pointers, nnz
+//   (knn_symmetrise.h)   the items sorted by (row, column), a pair combined by ts_combine, the kept entries emitted as CSR
 // Launches of one evaluation of the gradient:
 //   k_ts_repulse     the hot kernel.  Grid (row blocks, slices).  A lane owns TS_R = 2 rows i (y_i and three f32 accumulators
 //                    each in registers); the workgroup walks its slice of j in tiles of 128 positions staged in LDS and read
@@ -23,12 +21,13 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_kernels.h"
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_tsne.h"
+#include "knn_symmetrise.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int TS_TILE = GFICF_TSNE_TILE;     // positions j per LDS tile = the longest f32 accumulation chain
 constexpr int TS_R = 2;                      // rows per lane of the repulsion kernel
@@ -37,9 +36,9 @@ constexpr int TS_BLOCKS = 1024;              // workgroups the repulsion grid is
 constexpr int TS_GROUP = 8;                  // lanes per row of the update kernel
 constexpr int TS_UROWS = 256 / TS_GROUP;     // rows per workgroup of the update kernel
 constexpr int TS_MAX_STEPS = 200;            // evaluations of the bisection
-constexpr uint32_t TS_ST_ID = 1u;            // a neighbour id outside [1, N], a column of P outside [0, N)
-constexpr uint32_t TS_ST_VALUE = 2u;         // a non-finite distance or coordinate, a bad value of P
-constexpr uint32_t TS_ST_CSC = 4u;           // a row pointer of P that decreases or leaves [0, capacity]
+constexpr uint32_t TS_ST_ID = GFICF_AST_ID;          // a neighbour id outside [1, N], a column of P outside [0, N)
+constexpr uint32_t TS_ST_VALUE = GFICF_AST_VALUE;    // a non-finite distance or coordinate, a bad value of P
+constexpr uint32_t TS_ST_CSC = GFICF_AST_CSC;        // a row pointer of P that decreases or leaves [0, capacity]
 
 unsigned ts_grid(int64_t n) { return (unsigned)gficf_ceil_div(n > 0 ? n : 1, 256); }
 
@@ -129,99 +128,16 @@ __global__ __launch_bounds__(256) void k_ts_beta(const int32_t* __restrict__ idx
 }
 
 // ------------------------------------------------------------------------------------------------ affinities: symmetrisation
-// item t = 2 slot + dir, slot = m N + i (m = table column - 1): dir 0 is the entry (i, j) of Pc, dir 1 the entry (j, i) of Pc'
-struct TsItem { int32_t row, col; float w; };
-
-__device__ inline TsItem ts_item(uint32_t t, const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld) {
-  const int64_t slot = t >> 1, m = slot / N, i = slot % N;
-  const float w = W[slot];
-  TsItem it;
-  it.w = w;
-  if (!(w > 0.f)) {                                             // dropped: the self entry, a bad id, an underflow
-    it.row = (int32_t)N; it.col = 0;
-    return it;
-  }
-  const int32_t j = idx[(m + 1) * ld + i] - 1;                  // in [0, N): k_ts_beta zeroed the others
-  it.row = (t & 1u) ? j : (int32_t)i;
-  it.col = (t & 1u) ? (int32_t)i : j;
-  return it;
-}
-
-__global__ __launch_bounds__(256) void k_ts_key_col(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                    u64* __restrict__ kv) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= M) return;
-  const TsItem it = ts_item((uint32_t)t, idx, W, N, ld);
-  kv[t] = ((u64)(uint32_t)it.col << 32) | (u64)t;
-}
-
-__global__ __launch_bounds__(256) void k_ts_key_row(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                    const uint32_t* __restrict__ order, u64* __restrict__ kv) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= M) return;
-  const uint32_t t = order[p];
-  const TsItem it = ts_item(t, idx, W, N, ld);
-  kv[p] = ((u64)(uint32_t)it.row << 32) | (u64)t;
-}
-
 // the two conditionals of a pair, smaller first: both directions evaluate the same expression on the same operands
-__device__ inline float ts_combine(float x, float y, double two_n) {
-  const float lo = fminf(x, y), hi = fmaxf(x, y);
-  return (float)(((double)lo + (double)hi) / two_n);
-}
-
-__global__ __launch_bounds__(256) void k_ts_heads(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                  const uint32_t* __restrict__ item, int64_t* __restrict__ flag, int32_t* __restrict__ tcol,
-                                                  float* __restrict__ tval) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p > M) return;
-  if (p == M) { flag[p] = 0; return; }
-  const TsItem me = ts_item(item[p], idx, W, N, ld);
-  int64_t keep = 0;
-  if (me.row < N) {
-    bool head = true;
-    if (p > 0) {
-      const TsItem pr = ts_item(item[p - 1], idx, W, N, ld);
-      head = pr.row != me.row || pr.col != me.col;
-    }
-    if (head) {
-      float other = 0.f;
-      if (p + 1 < M) {
-        const TsItem nx = ts_item(item[p + 1], idx, W, N, ld);
-        if (nx.row == me.row && nx.col == me.col) other = nx.w;
-      }
-      const float v = ts_combine(me.w, other, 2.0 * (double)N);
-      tcol[p] = me.col;
-      tval[p] = v;
-      keep = v > 0.f ? 1 : 0;
-    }
+struct ts_combine {
+  double two_n;
+  __device__ float operator()(float x, float y) const {
+    const float lo = fminf(x, y), hi = fmaxf(x, y);
+    return (float)(((double)lo + (double)hi) / two_n);
   }
-  flag[p] = keep;
-}
-
-__global__ __launch_bounds__(256) void k_ts_emit(int64_t N, int64_t M, const uint32_t* __restrict__ srow, const int64_t* __restrict__ pos,
-                                                 const int32_t* __restrict__ tcol, const float* __restrict__ tval, int64_t* __restrict__ rowptr,
-                                                 int32_t* __restrict__ col, float* __restrict__ val, int64_t* __restrict__ nnz) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p > M) return;
-  const int64_t at = pos[p];
-  if (p < M && pos[p + 1] != at) {
-    col[at] = tcol[p];
-    val[at] = tval[p];
-  }
-  int64_t row = p < M ? (int64_t)srow[p] : N, prev = p > 0 ? (int64_t)srow[p - 1] : -1;
-  if (row > N) row = N;
-  if (prev > N) prev = N;
-  for (int64_t r = prev + 1; r <= row; ++r) rowptr[r] = at;     // the rows that begin here: this one and the empty ones before it
-  if (p == M) *nnz = at;
-}
+};
 
 // ------------------------------------------------------------------------------------------------ gradient: checks
-__device__ inline int64_t ts_nnz(const int64_t* rowptr, int64_t N, int64_t cap) {
-  const int64_t n = rowptr[N];
-  return n < 0 ? 0 : n > cap ? cap : n;
-}
-
 // one lane per row and per entry of P and per coordinate, whichever is more
 __global__ __launch_bounds__(256) void k_ts_check(int64_t N, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const float* __restrict__ val, int64_t cap, const float* __restrict__ Y,
@@ -233,7 +149,7 @@ __global__ __launch_bounds__(256) void k_ts_check(int64_t N, const int64_t* __re
     if (b < 0 || e < b || e > cap || (t == 0 && b != 0)) st |= TS_ST_CSC;
   }
   if (t < 2 * N && !isfinite(Y[t])) st |= TS_ST_VALUE;
-  if (t < ts_nnz(rowptr, N, cap)) {
+  if (t < gficf_addon_nnz(rowptr, N, cap)) {
     const int32_t j = col[t];
     const float w = val[t];
     if (j < 0 || (int64_t)j >= N) st |= TS_ST_ID;
@@ -431,38 +347,19 @@ __global__ __launch_bounds__(256) void k_ts_in(const double* __restrict__ init, 
   gains[t] = 1.f;
 }
 
-__global__ __launch_bounds__(256) void k_ts_out(const float* __restrict__ Y, int64_t N, double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2 * N) return;
-  out[(t & 1) * N + (t >> 1)] = (double)Y[t];
-}
-
 // ------------------------------------------------------------------------------------------------ workspaces
 struct TsAffWs {
   uint32_t* status;
   float* W;
-  u64 *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval;
-  int64_t* flag;
-  int32_t* tcol;
-  float* tval;
+  SymWs sym;
 };
 
 size_t ts_carve_aff(char* base, int64_t N, int K, TsAffWs& w) {
   gficf_carver cv;
   cv.base = base;
-  const size_t M = 2 * (size_t)N * (size_t)K;
   w.status = cv.take<uint32_t>(1);
   w.W = cv.take<float>((size_t)N * (size_t)K);
-  w.kv0 = cv.take<u64>(M);
-  w.kv1 = cv.take<u64>(M);
-  w.hist = cv.take<int64_t>((size_t)gficf_radix_sort_hist_len((int64_t)M, gficf_bit_width(N)));
-  w.okey = cv.take<uint32_t>(M);
-  w.oval = cv.take<uint32_t>(M);
-  w.flag = cv.take<int64_t>(M + 1);
-  w.tcol = cv.take<int32_t>(M);
-  w.tval = cv.take<float>(M);
+  sym_carve(cv, N, 2 * (size_t)N * (size_t)K, w.sym);
   return cv.total();
 }
 
@@ -524,26 +421,8 @@ int ts_affinities(gficf_ctx* ctx, const TsAffWs& w, const int32_t* d_idx, const 
                   int64_t* d_rowptr, int32_t* d_col, float* d_val, int64_t* d_nnz, double* d_beta) {
   hipStream_t st = ctx->stream;
   const int K = k - 1;
-  const int64_t M = 2 * N * K;
-  const int bits = gficf_bit_width(N);
   hipLaunchKernelGGL(k_ts_beta, dim3(ts_grid(N)), dim3(256), 0, st, d_idx, d_dist, N, K, ld, std::log(perplexity), w.W, d_beta, w.status);
-  hipLaunchKernelGGL(k_ts_key_col, dim3(ts_grid(M)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  int rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, M, bits, w.okey, w.oval);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ts_key_row, dim3(ts_grid(M)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, (const uint32_t*)w.oval, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, M, bits, w.okey, w.oval);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ts_heads, dim3(ts_grid(M + 1)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, (const uint32_t*)w.oval, w.flag,
-                     w.tcol, w.tval);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_exclusive_scan_i64(ctx, w.flag, M + 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ts_emit, dim3(ts_grid(M + 1)), dim3(256), 0, st, N, M, (const uint32_t*)w.okey, (const int64_t*)w.flag,
-                     (const int32_t*)w.tcol, (const float*)w.tval, d_rowptr, d_col, d_val, d_nnz);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  return sym_enqueue(ctx, w.sym, d_idx, 1, w.W, N, K, ld, ts_combine{2.0 * (double)N}, d_rowptr, d_col, d_val, d_nnz);
 }
 
 void ts_launch_check(hipStream_t st, const TsLayWs& w, int64_t N, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t cap,
@@ -688,11 +567,8 @@ int gficf_tsne_layout_device(gficf_ctx* ctx, int64_t N, const int64_t* d_rowptr,
 }
 
 int gficf_tsne_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & TS_ST_ID) GFICF_FAIL(GFICF_ERR_BAD_ID, "a neighbour id outside [1, N] or a column of P outside [0, N)");
   if (st & TS_ST_CSC) GFICF_FAIL(GFICF_ERR_BAD_CSC, "a row pointer of P decreases or leaves [0, capacity]");
@@ -755,7 +631,7 @@ int gficf_tsne_host(gficf_ctx* ctx, const double* X, int64_t N, int d, int64_t l
                        (float)final_momentum, (float)eta, exaggeration_factor, d_Y, d_uY, d_gains, kl ? d_kl : nullptr);
       }
       if (!rc) {
-        hipLaunchKernelGGL(k_ts_out, dim3(ts_grid(2 * N)), dim3(256), 0, st, (const float*)d_Y, N, d_emb);
+        hipLaunchKernelGGL(k_addon_out, dim3(ts_grid(2 * N)), dim3(256), 0, st, (const float*)d_Y, N, d_emb);
         io.e = hipGetLastError();
         io.down(embedding, d_emb, sizeof(double) * 2 * (size_t)N);
         if (kl) io.down(kl, d_kl, sizeof(double));

@@ -6,14 +6,9 @@
 //   k_um_dist_part, k_um_dist_fin   the sum of all N k distances over UM_RED fixed chunks, the chunks added in order (f64);
 //                                   non-finite distances flagged, negative ones taken as 0
 //   k_um_smooth      one lane per point: rho, the bisection for sigma, the floor, the k memberships; bad ids flagged
-//   k_um_key_col, (sort), k_um_key_row, (sort)   the items sorted by (row, column) with the library's stable radix passes:
-//                                   by column first, then by row; a dropped item carries the key N and sorts behind the rest
-//   k_um_heads       one lane per sorted item: the first of a (row, column) pair combines with its mirror, if that follows it
-//   (scan), k_um_emit   positions of the kept entries; columns, values, row pointers (a lane that sees a row change writes the
-//                                   pointers of the rows in between), nnz
-// No step looks at a row as a whole, so the in-degree of a point (up to N - 1) costs nothing special here.
+//   (knn_symmetrise.h)   the items sorted by (row, column), a pair combined by um_combine, the kept entries emitted as CSR
 // Launches of the layout stage:
-//   k_um_finite      the initial coordinates checked
+//   k_addon_finite   the initial coordinates checked (addon_kernels.h)
 //   k_um_wmax_part, k_um_wmax_fin, k_um_q   the largest value of P over fixed chunks; the 32-bit schedule word of every entry
 //   k_um_hubs        the vertices whose row is longer than UM_HUB_LEN, listed (an integer counter: the list's order is free,
 //                                   no result depends on it)
@@ -27,33 +22,25 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_kernels.h"
+#include "addon_status.h"
 #include "common.h"
 #include "gficf_umap.h"
+#include "knn_symmetrise.h"
+#include "umap_force.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int UM_RED = 128;                  // fixed chunks of a reduction (one workgroup each)
 constexpr int UM_HUB_LEN = 256;              // a row longer than this is walked by a whole wave
 constexpr int UM_GROUP = 8;                  // lanes per vertex otherwise
 constexpr int UM_HUB_WAVES = 1024;           // waves that share the hub list, at most
-constexpr uint32_t UM_ST_ID = 1u;            // a neighbour id outside [1, N], a column of P outside [0, N)
-constexpr uint32_t UM_ST_VALUE = 2u;         // a non-finite distance, a non-finite coordinate, a bad value of P
-constexpr uint32_t UM_ST_CSC = 4u;           // a row pointer of P that decreases or leaves [0, capacity]
+constexpr uint32_t UM_ST_ID = GFICF_AST_ID;          // a neighbour id outside [1, N], a column of P outside [0, N)
+constexpr uint32_t UM_ST_VALUE = GFICF_AST_VALUE;    // a non-finite distance, a non-finite coordinate, a bad value of P
+constexpr uint32_t UM_ST_CSC = GFICF_AST_CSC;        // a row pointer of P that decreases or leaves [0, capacity]
 
 // one lane per element: n stays below 2^32 + 2 here (N k < 2^31), so the blocks fit a grid's x dimension
 unsigned um_grid(int64_t n) { return (unsigned)gficf_ceil_div(n > 0 ? n : 1, 256); }
-
-// a distance as the graph takes it: the cosine and correlation metrics of the search (1 - cos in f32) can round a hair below 0
-__device__ inline float um_dist(float d) { return fmaxf(d, 0.f); }
-
-__device__ inline u64 um_mix(u64 z) {         // the splitmix64 finaliser
-  z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-  z ^= z >> 27; z *= 0x94d049bb133111ebull;
-  z ^= z >> 31;
-  return z;
-}
 
 // ------------------------------------------------------------------------------------------------ graph: sigma, rho, W
 __global__ __launch_bounds__(256) void k_um_dist_part(const float* __restrict__ dist, int64_t N, int k, int64_t ld, double* __restrict__ part,
@@ -66,7 +53,7 @@ __global__ __launch_bounds__(256) void k_um_dist_part(const float* __restrict__ 
   for (int64_t t = lo + threadIdx.x; t < hi; t += 256) {
     const float d = dist[(t / N) * ld + t % N];
     bad |= !isfinite(d);
-    s += (double)um_dist(d);
+    s += (double)uf_dist(d);
   }
   if (bad) atomicOr(status, UM_ST_VALUE);
   sh[threadIdx.x] = s;
@@ -92,7 +79,7 @@ __global__ __launch_bounds__(256) void k_um_smooth(const int32_t* __restrict__ i
   int cnt = 0;
   float nz_lo = 0.f, nz_hi = 0.f, nz_max = 0.f, rowsum = 0.f;
   for (int c = 0; c < k; ++c) {
-    const float d = um_dist(dist[(int64_t)c * ld + i]);
+    const float d = uf_dist(dist[(int64_t)c * ld + i]);
     rowsum += d;
     if (c >= 1 && d > 0.f) {
       ++cnt;
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(256) void k_um_smooth(const int32_t* __restrict__ i
   for (int it = 0; it < 64; ++it) {
     float psum = 0.f;
     for (int c = 1; c < k; ++c) {
-      const float x = um_dist(dist[(int64_t)c * ld + i]) - rho;
+      const float x = uf_dist(dist[(int64_t)c * ld + i]) - rho;
       psum += x > 0.f ? expf(-x / mid) : 1.f;
     }
     if (fabsf(psum - target) < 1e-5f) break;
@@ -132,7 +119,7 @@ __global__ __launch_bounds__(256) void k_um_smooth(const int32_t* __restrict__ i
   bool bad = false;
   for (int c = 0; c < k; ++c) {
     const int32_t j = idx[(int64_t)c * ld + i];
-    const float x = um_dist(dist[(int64_t)c * ld + i]) - rho;
+    const float x = uf_dist(dist[(int64_t)c * ld + i]) - rho;
     float w;
     if (j < 1 || (int64_t)j > N) {
       bad = true;
@@ -150,109 +137,20 @@ __global__ __launch_bounds__(256) void k_um_smooth(const int32_t* __restrict__ i
 }
 
 // ------------------------------------------------------------------------------------------------ graph: symmetrisation
-// item t = 2 slot + dir, slot = c N + i: dir 0 is the entry (i, j) of W, dir 1 the entry (j, i) of its transpose
-struct UmItem { int32_t row, col; float w; };
-
-__device__ inline UmItem um_item(uint32_t t, const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld) {
-  const int64_t slot = t >> 1, c = slot / N, i = slot % N;
-  const float w = W[slot];
-  UmItem it;
-  it.w = w;
-  if (!(w > 0.f)) {                                             // dropped: the self entry, a bad id, an underflow
-    it.row = (int32_t)N; it.col = 0;
-    return it;
-  }
-  const int32_t j = idx[c * ld + i] - 1;                        // in [0, N): k_um_smooth zeroed the others
-  it.row = (t & 1u) ? j : (int32_t)i;
-  it.col = (t & 1u) ? (int32_t)i : j;
-  return it;
-}
-
-__global__ __launch_bounds__(256) void k_um_key_col(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                    u64* __restrict__ kv) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= M) return;
-  const UmItem it = um_item((uint32_t)t, idx, W, N, ld);
-  kv[t] = ((u64)(uint32_t)it.col << 32) | (u64)t;
-}
-
-__global__ __launch_bounds__(256) void k_um_key_row(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                    const uint32_t* __restrict__ order, u64* __restrict__ kv) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= M) return;
-  const uint32_t t = order[p];
-  const UmItem it = um_item(t, idx, W, N, ld);
-  kv[p] = ((u64)(uint32_t)it.row << 32) | (u64)t;
-}
-
 // the two memberships of a pair, smaller first: both directions evaluate the same expression on the same operands
-__device__ inline float um_combine(float x, float y, float mix) {
-  const float lo = fminf(x, y), hi = fmaxf(x, y), prod = lo * hi;
-  return mix * ((lo + hi) - prod) + (1.f - mix) * prod;
-}
-
-__global__ __launch_bounds__(256) void k_um_heads(const int32_t* __restrict__ idx, const float* __restrict__ W, int64_t N, int64_t ld, int64_t M,
-                                                  const uint32_t* __restrict__ item, float mix, int64_t* __restrict__ flag,
-                                                  int32_t* __restrict__ tcol, float* __restrict__ tval) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p > M) return;
-  if (p == M) { flag[p] = 0; return; }
-  const UmItem me = um_item(item[p], idx, W, N, ld);
-  int64_t keep = 0;
-  if (me.row < N) {
-    bool head = true;
-    if (p > 0) {
-      const UmItem pr = um_item(item[p - 1], idx, W, N, ld);
-      head = pr.row != me.row || pr.col != me.col;
-    }
-    if (head) {
-      float other = 0.f;
-      if (p + 1 < M) {
-        const UmItem nx = um_item(item[p + 1], idx, W, N, ld);
-        if (nx.row == me.row && nx.col == me.col) other = nx.w;
-      }
-      const float v = um_combine(me.w, other, mix);
-      tcol[p] = me.col;
-      tval[p] = v;
-      keep = v > 0.f ? 1 : 0;
-    }
+struct um_combine {
+  float mix;
+  __device__ float operator()(float x, float y) const {
+    const float lo = fminf(x, y), hi = fmaxf(x, y), prod = lo * hi;
+    return mix * ((lo + hi) - prod) + (1.f - mix) * prod;
   }
-  flag[p] = keep;
-}
-
-__global__ __launch_bounds__(256) void k_um_emit(int64_t N, int64_t M, const uint32_t* __restrict__ srow, const int64_t* __restrict__ pos,
-                                                 const int32_t* __restrict__ tcol, const float* __restrict__ tval, int64_t* __restrict__ rowptr,
-                                                 int32_t* __restrict__ col, float* __restrict__ val, int64_t* __restrict__ nnz) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p > M) return;
-  const int64_t at = pos[p];
-  if (p < M && pos[p + 1] != at) {
-    col[at] = tcol[p];
-    val[at] = tval[p];
-  }
-  int64_t row = p < M ? (int64_t)srow[p] : N, prev = p > 0 ? (int64_t)srow[p - 1] : -1;
-  if (row > N) row = N;
-  if (prev > N) prev = N;
-  for (int64_t r = prev + 1; r <= row; ++r) rowptr[r] = at;     // the rows that begin here: this one and the empty ones before it
-  if (p == M) *nnz = at;
-}
+};
 
 // ------------------------------------------------------------------------------------------------ layout: schedule
-__global__ __launch_bounds__(256) void k_um_finite(const float* __restrict__ Y, int64_t n, uint32_t* __restrict__ status) {
-  bool bad = false;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) bad |= !isfinite(Y[t]);
-  if (bad) atomicOr(status, UM_ST_VALUE);
-}
-
-__device__ inline int64_t um_nnz(const int64_t* rowptr, int64_t N, int64_t cap) {
-  const int64_t n = rowptr[N];
-  return n < 0 ? 0 : n > cap ? cap : n;
-}
-
 __global__ __launch_bounds__(256) void k_um_wmax_part(const float* __restrict__ val, const int64_t* __restrict__ rowptr, int64_t N, int64_t cap,
                                                       float* __restrict__ part, uint32_t* __restrict__ status) {
   __shared__ float sh[256];
-  const int64_t total = um_nnz(rowptr, N, cap), per = gficf_ceil_div(total, UM_RED);
+  const int64_t total = gficf_addon_nnz(rowptr, N, cap), per = gficf_ceil_div(total, UM_RED);
   const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < total ? lo + per : total;
   float m = 0.f;
   bool bad = false;
@@ -284,7 +182,7 @@ __global__ __launch_bounds__(256) void k_um_q(const float* __restrict__ val, con
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cap) return;
   uint32_t qe = 0u;
-  if (e < um_nnz(rowptr, N, cap)) {
+  if (e < gficf_addon_nnz(rowptr, N, cap)) {
     const float w = val[e];
     const int32_t j = col[e];
     if (j < 0 || (int64_t)j >= N) atomicOr(status, UM_ST_ID);
@@ -325,43 +223,6 @@ struct UmLay {
   u64 seed;
 };
 
-__device__ inline float um_clip(float x) { return fminf(fmaxf(x, -4.f), 4.f); }
-
-template <bool T1>
-__device__ inline void um_attract(float& yx, float& yy, float jx, float jy, float alpha, const UmLay& L) {
-  const float dx = yx - jx, dy = yy - jy, d2 = dx * dx + dy * dy;
-  float coef = 0.f;
-  if (d2 > 0.f) {
-    if (T1) {
-      coef = -2.f / (d2 + 1.f);
-    } else {
-      const float pd = powf(d2, L.b);
-      coef = (L.m2ab * pd) / (d2 * (L.a * pd + 1.f));
-    }
-  }
-  yx += alpha * um_clip(coef * dx);
-  yy += alpha * um_clip(coef * dy);
-}
-
-template <bool T1>
-__device__ inline void um_repulse(float& yx, float& yy, float jx, float jy, float alpha, const UmLay& L) {
-  const float dx = yx - jx, dy = yy - jy, d2 = dx * dx + dy * dy;
-  float sx = 4.f, sy = 4.f;
-  if (d2 > 0.f) {
-    float coef;
-    if (T1) {
-      coef = L.g2b / ((0.001f + d2) * (d2 + 1.f));
-    } else {
-      const float pd = powf(d2, L.b);
-      coef = L.g2b / ((0.001f + d2) * (L.a * pd + 1.f));
-    }
-    sx = um_clip(coef * dx);
-    sy = um_clip(coef * dy);
-  }
-  yx += alpha * sx;
-  yy += alpha * sy;
-}
-
 // vertex v by the G lanes lane0 .. lane0 + G - 1 of a wave (all of them here, with the same v)
 template <int G, bool T1>
 __device__ inline void um_vertex(const UmLay& L, int32_t v, const float2* __restrict__ Ycur, float2* __restrict__ Ynext, int n, float alpha) {
@@ -371,7 +232,7 @@ __device__ inline void um_vertex(const UmLay& L, int32_t v, const float2* __rest
   if (e1 > L.cap) e1 = L.cap;
   const float2 y0 = Ycur[v];
   float yx = y0.x, yy = y0.y;
-  const u64 kn = um_mix(L.seed + (u64)n), un = (u64)n;
+  const u64 kn = uf_mix(L.seed + (u64)n), un = (u64)n;
   for (int64_t base = e0; base < e1; base += G) {
     const int64_t e = base + lane;
     bool due = false;
@@ -387,25 +248,25 @@ __device__ inline void um_vertex(const UmLay& L, int32_t v, const float2* __rest
     while (mask) {                                              // the same in every lane of the group
       const int t = __builtin_ctzll(mask);
       mask &= mask - 1ull;
-      const u64 ke = um_mix(kn + (u64)(base + t));
+      const u64 ke = uf_mix(kn + (u64)(base + t));
       for (int s0 = 0;; s0 += G) {                              // the first round also applies the attraction
         int32_t jn = v;                                         // v: no sample
         float2 yn = make_float2(0.f, 0.f);
         if (s0 + lane < L.rate) {
-          const u64 key = um_mix(ke + (u64)(s0 + lane));
+          const u64 key = uf_mix(ke + (u64)(s0 + lane));
           jn = (int32_t)(((key >> 32) * (u64)L.N) >> 32);
           if (jn != v) yn = Ycur[jn];
         }
         if (s0 == 0) {
           const float jx = __shfl(yj.x, t, G), jy = __shfl(yj.y, t, G);
-          um_attract<T1>(yx, yy, jx, jy, alpha, L);
-          um_attract<T1>(yx, yy, jx, jy, alpha, L);
+          uf_attract<T1>(yx, yy, jx, jy, alpha, L);
+          uf_attract<T1>(yx, yy, jx, jy, alpha, L);
         }
         const int cnt = L.rate - s0 < G ? L.rate - s0 : G;
         for (int u = 0; u < cnt; ++u) {
           const int32_t ju = __shfl(jn, u, G);
           const float nx = __shfl(yn.x, u, G), ny = __shfl(yn.y, u, G);
-          if (ju != v) um_repulse<T1>(yx, yy, nx, ny, alpha, L);
+          if (ju != v) uf_repulse<T1>(yx, yy, nx, ny, alpha, L);
         }
         if (s0 + G >= L.rate) break;
       }
@@ -440,42 +301,23 @@ __global__ __launch_bounds__(256) void k_um_in(const double* __restrict__ init, 
   Y[t] = (float)x;
 }
 
-__global__ __launch_bounds__(256) void k_um_out(const float* __restrict__ Y, int64_t N, double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= 2 * N) return;
-  out[(t & 1) * N + (t >> 1)] = (double)Y[t];
-}
-
 // ------------------------------------------------------------------------------------------------ workspaces
 struct UmGraphWs {
   uint32_t* status;
   double* part;
   float* mean;
   float* W;
-  u64 *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval;
-  int64_t* flag;
-  int32_t* tcol;
-  float* tval;
+  SymWs sym;
 };
 
 size_t um_carve_graph(char* base, int64_t N, int k, UmGraphWs& w) {
   gficf_carver cv;
   cv.base = base;
-  const size_t M = 2 * (size_t)N * (size_t)k;
   w.status = cv.take<uint32_t>(1);
   w.part = cv.take<double>(UM_RED);
   w.mean = cv.take<float>(1);
   w.W = cv.take<float>((size_t)N * (size_t)k);
-  w.kv0 = cv.take<u64>(M);
-  w.kv1 = cv.take<u64>(M);
-  w.hist = cv.take<int64_t>((size_t)gficf_radix_sort_hist_len((int64_t)M, gficf_bit_width(N)));
-  w.okey = cv.take<uint32_t>(M);
-  w.oval = cv.take<uint32_t>(M);
-  w.flag = cv.take<int64_t>(M + 1);
-  w.tcol = cv.take<int32_t>(M);
-  w.tval = cv.take<float>(M);
+  sym_carve(cv, N, 2 * (size_t)N * (size_t)k, w.sym);
   return cv.total();
 }
 
@@ -530,37 +372,19 @@ int um_check_layout(int64_t N, int64_t cap, double a, double b, double gamma, do
 int um_graph(gficf_ctx* ctx, const UmGraphWs& w, const int32_t* d_idx, const float* d_dist, int64_t N, int k, int64_t ld, double lc, double mix,
              int64_t* d_rowptr, int32_t* d_col, float* d_val, int64_t* d_nnz, float* d_sigma, float* d_rho) {
   hipStream_t st = ctx->stream;
-  const int64_t M = 2 * N * k;
-  const int bits = gficf_bit_width(N);
   const int lcf = (int)std::floor(lc);
   hipLaunchKernelGGL(k_um_dist_part, dim3(UM_RED), dim3(256), 0, st, d_dist, N, k, ld, w.part, w.status);
   hipLaunchKernelGGL(k_um_dist_fin, dim3(1), dim3(1), 0, st, (const double*)w.part, N * k, w.mean);
   hipLaunchKernelGGL(k_um_smooth, dim3(um_grid(N)), dim3(256), 0, st, d_idx, d_dist, N, k, ld, lcf, (float)(lc - (double)lcf), (const float*)w.mean,
                      w.W, d_sigma, d_rho, w.status);
-  hipLaunchKernelGGL(k_um_key_col, dim3(um_grid(M)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  int rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, M, bits, w.okey, w.oval);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_um_key_row, dim3(um_grid(M)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, (const uint32_t*)w.oval, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, M, bits, w.okey, w.oval);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_um_heads, dim3(um_grid(M + 1)), dim3(256), 0, st, d_idx, (const float*)w.W, N, ld, M, (const uint32_t*)w.oval, (float)mix,
-                     w.flag, w.tcol, w.tval);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_exclusive_scan_i64(ctx, w.flag, M + 1);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_um_emit, dim3(um_grid(M + 1)), dim3(256), 0, st, N, M, (const uint32_t*)w.okey, (const int64_t*)w.flag,
-                     (const int32_t*)w.tcol, (const float*)w.tval, d_rowptr, d_col, d_val, d_nnz);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  return sym_enqueue(ctx, w.sym, d_idx, 0, w.W, N, k, ld, um_combine{(float)mix}, d_rowptr, d_col, d_val, d_nnz);
 }
 
 // the layout stage, likewise
 int um_layout(gficf_ctx* ctx, const UmLayoutWs& w, int64_t N, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t cap, float a,
               float b, float gamma, float lr, int rate, int n_epochs, int eb, int ee, uint64_t seed, float* d_Y) {
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_um_finite, dim3(um_grid(2 * N) < 1024 ? um_grid(2 * N) : 1024), dim3(256), 0, st, (const float*)d_Y, 2 * N, w.status);
+  hipLaunchKernelGGL(k_addon_finite, dim3(um_grid(2 * N) < 1024 ? um_grid(2 * N) : 1024), dim3(256), 0, st, (const float*)d_Y, 2 * N, w.status);
   hipLaunchKernelGGL(k_um_wmax_part, dim3(UM_RED), dim3(256), 0, st, d_val, d_rowptr, N, cap, w.part, w.status);
   hipLaunchKernelGGL(k_um_wmax_fin, dim3(1), dim3(1), 0, st, (const float*)w.part, w.wmax, w.nhubs);
   if (cap > 0)
@@ -643,11 +467,8 @@ int gficf_umap_layout_device(gficf_ctx* ctx, int64_t N, const int64_t* d_rowptr,
 }
 
 int gficf_umap_sync(gficf_ctx* ctx, const void* ws) {
-  GFICF_CTX_ENTER(ctx);
-  if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  uint32_t st = 0;
-  GFICF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  const int rc = gficf_ctx_sync(ctx);
+  uint32_t st;
+  const int rc = gficf_addon_read_status(ctx, ws, &st);
   if (rc) return rc;
   if (st & UM_ST_ID) GFICF_FAIL(GFICF_ERR_BAD_ID, "a neighbour id outside [1, N] or a column of the graph outside [0, N)");
   if (st & UM_ST_CSC) GFICF_FAIL(GFICF_ERR_BAD_CSC, "a row pointer of the graph decreases or leaves [0, capacity]");
@@ -709,7 +530,7 @@ int gficf_umap_host(gficf_ctx* ctx, const double* X, int64_t N, int d, int64_t l
                        n_epochs, 0, n_epochs, seed, d_Y);
       }
       if (!rc) {
-        hipLaunchKernelGGL(k_um_out, dim3(um_grid(2 * N)), dim3(256), 0, st, (const float*)d_Y, N, d_emb);
+        hipLaunchKernelGGL(k_addon_out, dim3(um_grid(2 * N)), dim3(256), 0, st, (const float*)d_Y, N, d_emb);
         io.e = hipGetLastError();
         io.down(embedding, d_emb, sizeof(double) * 2 * (size_t)N);
         if (idx) io.down(idx, d_idx, sizeof(int32_t) * nk);

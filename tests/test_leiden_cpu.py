@@ -3,6 +3,7 @@
 the argument handling of the Python mirror (everything it decides before the first call into the library)."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -31,10 +32,14 @@ def test_header_and_loader_name_the_same_entries():
 
 
 def test_makefile_builds_the_library_with_the_others():
-    mk = open(os.path.join(ROOT, "gficf_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^all:.*\$\(LEIDEN_OUT\)", mk, re.M) and "libgficf_leiden.so" in mk
-    assert re.search(r"^\s+rm -f .*leiden\.o \$\(LEIDEN_OUT\)", mk, re.M)
-    assert re.search(r"^\$\(LEIDEN_OUT\): leiden\.o \$\(OUT\)\n\t\$\(HIPCC\) --offload-arch=\$\(ARCH\) -shared -fPIC -o \$@ leiden\.o -L\.\. -lgficf_hip", mk, re.M)
+    # what make itself would run (a dry run of everything, nothing is compiled): the rules are free to be shared with the other add-ons
+    csrc = os.path.join(ROOT, "gficf_amd", "csrc")
+    build = subprocess.run(["make", "-n", "-B", "-C", csrc, "all"], capture_output=True, text=True, check=True).stdout.splitlines()
+    link = [ln for ln in build if " -o ../libgficf_leiden.so " in ln]
+    assert len(link) == 1 and re.search(r"hipcc --offload-arch=gfx950 -shared -fPIC -o \.\./libgficf_leiden\.so leiden\.o -L\.\. -lgficf_hip\b", link[0])
+    assert build.index(link[0]) > max(i for i, ln in enumerate(build) if " -o ../libgficf_hip.so " in ln or ln.endswith(" -o leiden.o"))
+    clean = subprocess.run(["make", "-n", "-C", csrc, "clean"], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"^rm -f .*\bleiden\.o\b.* \.\./libgficf_leiden\.so\b", clean, re.M)
 
 
 @pytest.mark.parametrize("name", ["knn_blobs", "knn_noise_alg2", "planted3", "planted8_res08"])
