@@ -259,7 +259,8 @@ __global__ __launch_bounds__(256) void k_ld_move(LdG g, double r, int s, int t, 
   }
 }
 
-// a wave per vertex: the decided moves applied to labels, totals and sizes; the mover's neighbours stamped for another look
+// a wave per vertex: the decided moves applied to labels, totals and sizes; the mover's neighbours (the targets of its entries of
+// non-zero weight: a self-loop of a coarser level stamps the mover itself) stamped for another look
 __global__ __launch_bounds__(256) void k_ld_apply(LdG g, int t, int32_t* __restrict__ comm, const int32_t* __restrict__ next, u64* __restrict__ K,
                                                   int32_t* __restrict__ size, int32_t* __restrict__ mark, u64* __restrict__ scal) {
   const int lane = threadIdx.x & 63;
@@ -277,7 +278,8 @@ __global__ __launch_bounds__(256) void k_ld_apply(LdG g, int t, int32_t* __restr
       atomicSub(&size[old], 1);
       *(uint32_t*)(scal + LD_S_CHANGED) = 1u;
     }
-    for (int64_t e = g.beg[v] + lane; e < g.end[v]; e += 64) mark[g.nbr[e]] = t;
+    for (int64_t e = g.beg[v] + lane; e < g.end[v]; e += 64)
+      if (g.wt[e]) mark[g.nbr[e]] = t;      // a stored zero, and the level-0 diagonal (k_ld_fix: 0), is no edge and carries no stamp
   }
 }
 

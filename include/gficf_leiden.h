@@ -37,7 +37,27 @@
  *     (vertex, seed, level); sub-round s of an iteration moves class s on one snapshot of the labels and totals, and the totals
  *     are applied between sub-rounds.  Two singletons never swap (the one with the smaller label stays).  The hash does not
  *     depend on the iteration number: leiden(n_iterations = 2) == leiden(1) resumed from leiden(1)'s labels, bit for bit.
- *     A pass over the four classes that lowers Q is undone and ends the level; at most 64 passes a level;
+ *     A pass over the four classes that lowers Q is undone and ends the level; at most 64 passes a level.
+ *     THE CLASS of vertex v of a level is h(v ^ hseed) % 4, with
+ *         h(v):  v ^= v >> 16;  v *= 0x7feb352d;  v ^= v >> 15;  v *= 0x846ca68b;  v ^= v >> 16        (uint32_t)
+ *         hseed = h(seed * 0x9E3779B1 + level * 0x85EBCA77 + 0x165667B1)                               (uint32_t, level from 0)
+ *     THE STAMP.  Sub-rounds are counted t = 1, 2, ... from the start of the level (sub-round s of pass p: t = 4 p + s + 1).
+ *     Every vertex that moves in sub-round t stamps t on the target of each of its entries of NON-ZERO weight — a stored zero
+ *     and the level-0 diagonal are no edges and carry no stamp; the self-loop of a coarser level has weight and stamps the
+ *     mover itself.  A vertex of class s is looked at in sub-round t iff t <= 4 (the first pass: everybody) or its stamp is
+ *     >= t - 4 (something next to it moved since its last turn, that turn's own sub-round included).
+ *     THE DECISION of v, on the labels, totals and sizes as they stood before the sub-round: its candidates are the communities
+ *     other than its own that an entry (u != v, weight != 0) leads to; none: it stays.  The best is the one of largest gain,
+ *     ties to the smaller label; v moves iff best > stay or (best == stay and the best label is smaller than its own), where
+ *     stay = e(v, own) - resolution * k_v (K_own - k_v) / 2W; a singleton does not move to a singleton of larger label.  All
+ *     moves of a sub-round are applied together.  After the pass: nothing moved ends the level; Q lower than before the pass
+ *     restores the snapshot and ends the level (Q in f64: where the exact values are equal the rounding of sum K^2 decides —
+ *     DESIGN.md section 15, "exact ties");
+ *   * the numbers: a weight is llrint(x * 2^32), and 0 on the diagonal of the matrix; k_v is the sum of row v and 2W the sum
+ *     of all k_v; a vertex of a coarser level has the summed k of its members (which includes its self-loop).  Gains and the
+ *     tests of the refinement are evaluated in f64 from these integers (r = resolution / 2W rounded once): a comparison whose
+ *     sides differ by less than the f64 rounding of their terms may fall either way between builds of this library, never
+ *     between calls;
  *   * refinement in rounds.  Every eligible singleton v proposes its best target among the refined communities that had more
  *     than one member at the start of the round and the singletons of smaller id than v.  A proposal commits iff the target
  *     had more than one member at the start of the round or its single member proposed nothing this round.  Rounds repeat
@@ -47,10 +67,15 @@
  *     move, a singleton that is joined proposed nothing and stays: every commit joins v to a community that still holds the
  *     neighbour it saw, so every refined community is connected.  Several vertices may join one r in a round on start-of-round
  *     figures (K_r, E(r, C - r), recomputed before the next round): only the refined partition's structure is contracted,
- *     not each gain;
+ *     not each gain.
+ *     In other words a proposal of v to p commits iff p itself proposed nothing.  e(v, C - v) is computed once; K_r and
+ *     E(r, C - r) are recomputed after every round that commits; a refined community's label is the id of the singleton it
+ *     grew from;
  *   * aggregation: every vertex sums its entries per neighbouring refined community and appends one entry per community to
  *     the row of its own (rows in begin / end form; a row may name a neighbour once per member vertex — every consumer sums
- *     per community anyway).
+ *     per community anyway).  The new vertices are the refined communities in ascending order of their labels; entries of
+ *     weight 0 are dropped, self-loops kept; a new vertex starts in the smallest new id among its old community's members.
+ *     At most 64 levels.  Between iterations a community is relabelled by its smallest member.
  *   Rows up to 128 entries are handled by one wave with a 256-slot LDS table, longer ones by a workgroup with a 4096-slot
  *   table, in ceil(min(entries, vertices of the level) / 1024) passes over the row by hash class of the community.
  *   GFICF_ERR_UNSUPPORTED only if one such class overflows the table (not observed).  No floating-point atomics.
