@@ -2,7 +2,8 @@
 tests/test_transform_gpu.py (the library), so that both are held to the same statements.
 
 ``python -m tests.helpers.transform_cases`` recomputes, on the CPU and with the port alone, the MEASURED tables that
-tests/test_transform_gpu.py carries (the f32 / f64 deviation of every layout case, the port's hold-out figures)."""
+tests/test_transform_gpu.py and tests/test_transform_exact_gpu.py carry (the f32 / f64 deviation of every layout case, the
+port's hold-out figures)."""
 import functools
 
 import numpy as np
@@ -92,16 +93,19 @@ RATES = (0, 1, 8, 9, 20)
 
 
 @functools.lru_cache(maxsize=None)
-def layout_case(name):
+def layout_case(name, k=LAYOUT_K):
     """(idx, W, Y_train, Y0) by the port: 500 new cells against a trained layout of 1 500 points (umap_cases.random_input and
-    plane_init at that size: the recipe of umap_cases.layout_graph("rand")).  "crafted": the cells of CRAFTED start exactly on the
-    trained cell of their column 0, whose entry has the row's largest membership and so is due in every epoch but the first."""
+    plane_init at that size: the recipe of umap_cases.layout_graph("rand")), k neighbours each.  "crafted": the cells of CRAFTED
+    start exactly on the trained cell of their column 0, whose entry has the row's largest membership and so is due in every
+    epoch but the first."""
     X = uc.random_input(1500)
     Yt = uc.plane_init(X).astype(np.float32)
     Q = uc.random_input(500, seed=6)
-    idx, dist = tn.query_knn(X, Q, LAYOUT_K)
+    idx, dist = tn.query_knn(X, Q, k)
     _, _, W = tn.memberships(dist)
     Y0 = tn.init_positions(idx, W, Yt)
+    if k == 1:                       # the weighted mean of one head is that head, and a cell on its only head moves by samples alone:
+        Y0 = layout_case("rand")[3]  # a given start instead (umap_transform takes one), that of the case with LAYOUT_K neighbours
     if name == "crafted":
         Y0 = Y0.copy()
         Y0[CRAFTED] = Yt[idx[CRAFTED, 0] - 1]
@@ -125,6 +129,67 @@ def rate_kw(rate):
 
 def tolerance(measured):
     return max(8.0 * measured, FLOOR)
+
+
+# ------------------------------------------------------------------------------------------------ exact cases
+# What tests/test_transform_exact_gpu.py holds to the bits of the float32 port, and tests/test_transform_cpu.py keeps from being
+# vacuous: layout_case() at the k around the 8 lanes of a group, cut to M cells around the 8 cells of a workgroup.
+GROUP = 8                            # TR_GROUP of transform.hip: lanes per new cell, and cells per workgroup
+EXACT_KS = (1, 7, 8, 9, 16, 17, 128)
+EXACT_MS = (1, 7, 8, 9, 500)
+EXACT_RATES = (0, 7, 8, 9, 17)
+EXACT_WINDOW = (30, 32)              # two epochs: the running position is carried from one to the next in registers
+EXACT_SEED = 3
+EXACT_CRAFTED_K = 8
+EXACT_OFFSETS = ((250, 250), (0, 2 ** 40 + 3))      # (first row of the block, its query_offset)
+INIT_KS = (1, 2, 15, 128)
+INIT_ZERO_ROW = 3
+
+
+def exact_kw(rate, query_offset=0):
+    lo, hi = EXACT_WINDOW
+    return dict(learning_rate=LAYOUT_LR, negative_sample_rate=rate, seed=EXACT_SEED, query_offset=query_offset, epoch_begin=lo, epoch_end=hi)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_port(name, k, rate, dtype=np.float32, first=0, query_offset=0):
+    """The port's result, in ``dtype``, for the rows from ``first`` on of layout_case(name, k) on the t-UMAP curve; computed
+    once, not to be written to.  Cell i of it depends on row i and query_offset + i only (include/gficf_transform.h; the port's
+    own statement of that is tests/test_transform_cpu.py), so its first M rows are the result for the first M rows."""
+    idx, W, Yt, Y0 = layout_case(name, k)
+    Y = tn.layout(idx[first:], W[first:], Yt, Y0[first:], LAYOUT_EPOCHS, dtype=dtype, **exact_kw(rate, query_offset))
+    Y.setflags(write=False)
+    return Y
+
+
+def exact_cases():
+    """(input, k, negative_sample_rate): every k at every rate, and the crafted coincidence at k = 8."""
+    return [("rand", k, r) for k in EXACT_KS for r in EXACT_RATES] + [("crafted", EXACT_CRAFTED_K, r) for r in (0, 7)]
+
+
+def round_coverage(W, n):
+    """What the row-local schedule of epoch n does to the rounds of GROUP columns a row is walked in: ``first`` / ``last``: a due
+    entry sits in lane slot 0 / GROUP - 1; ``ragged``: a due entry sits in a last round of fewer than GROUP columns; ``empty``:
+    some round of some row has no due entry."""
+    M, k = W.shape
+    fire = np.stack([tn.due(tn.row_schedule(W)[:, c], n) for c in range(k)], axis=1)
+    c = np.arange(k)
+    per_round = np.add.reduceat(fire.astype(np.int64), np.arange(0, k, GROUP), axis=1)
+    return dict(first=bool(fire[:, c % GROUP == 0].any()), last=bool(fire[:, c % GROUP == GROUP - 1].any()),
+                ragged=bool(fire[:, c // GROUP == k // GROUP].any()), empty=bool((per_round == 0).any()))
+
+
+@functools.lru_cache(maxsize=None)
+def init_case(k):
+    """(idx, W, Y_train): 300 new cells (two workgroups of the one-lane-per-cell kernel) against 400 trained ones; memberships
+    uniform in (0, 1] with a tenth of them 0, and row INIT_ZERO_ROW all 0: the plain mean."""
+    rng = np.random.default_rng(500 + k)
+    N, M = 400, 300
+    idx = np.stack([rng.choice(N, size=k, replace=False) for _ in range(M)]).astype(np.int32) + 1
+    W = (1.0 - rng.random((M, k))).astype(np.float32)
+    W[rng.random((M, k)) < 0.1] = 0.0
+    W[INIT_ZERO_ROW] = 0.0
+    return idx, W, rng.uniform(-10.0, 10.0, size=(N, 2)).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ hold-out
@@ -247,6 +312,11 @@ def _main():
         dev = float(np.abs(tn.layout(idx, W, Yt, Y0, LAYOUT_EPOCHS, dtype=np.float32, **kw).astype(np.float64)
                            - tn.layout(idx, W, Yt, Y0, LAYOUT_EPOCHS, dtype=np.float64, **kw)).max())
         print(f"    {rate}: {dev:.3e},")
+    print("}")
+    print("MEASURED_EXACT = {      # case: (cells compared, |port f32 - port f64|)")
+    for case in exact_cases():
+        f32 = exact_port(*case, np.float32)
+        print(f"    {case!r}: ({len(f32)}, {float(np.abs(f32.astype(np.float64) - exact_port(*case, np.float64)).max()):.3e}),")
     print("}")
     cells_tr, lab_tr, cells_te, lab_te, _, _ = holdout()
     nn_idx, nn_dist = un.exact_knn(cells_tr, 15)

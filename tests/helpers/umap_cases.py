@@ -2,7 +2,8 @@
 library), so that both are held to the same statements.
 
 ``python -m tests.helpers.umap_cases`` recomputes, on the CPU and with the port alone, the MEASURED tables that
-tests/test_umap_gpu.py carries (the f32 / f64 deviation of every layout case, the port's quality figures)."""
+tests/test_umap_gpu.py and tests/test_umap_exact_gpu.py carry (the f32 / f64 deviation of every layout case, the port's quality
+figures)."""
 import functools
 
 import numpy as np
@@ -198,6 +199,189 @@ def tolerance(measured):
     return max(8.0 * measured, FLOOR)
 
 
+# ------------------------------------------------------------------------------------------------ exact cases: crafted shapes
+# What tests/test_umap_exact_gpu.py holds to the bits of the float32 port, and tests/test_umap_cpu.py keeps from being vacuous.
+HUB_LEN = 256                        # UM_HUB_LEN of umap.hip: a longer row is walked by a whole wave, 64 entries a round
+GROUP, WAVE = 8, 64                  # lanes per vertex on the two paths
+HUB_WAVES = 1024                     # UM_HUB_WAVES: with more hubs than this a wave takes a second one
+SEAM_LENGTHS = (0, 1, 2, 7, 8, 9, 15, 16, 17, 24, 25, 63, 64, 65, 255, 256, 257, 258, 299, 0)      # rows 0 .. 19 of seams()
+SEAM_SHARED = slice(100, 130)        # the vertices of seams() that start at one position; their rows name each other only
+SEAM_RATES = (0, 1, 5, 7, 8, 9, 16, 17, 63, 64, 65, 130)
+WINDOWS = {"0-1": (0, 1), "100-101": (100, 101), "100-102": (100, 102), "100-103": (100, 103), "0-3": (0, 3)}
+PAD_VALUE = 1e-12                    # a value whose schedule word is 0 beside a largest value of 0.05 or more
+PADDED = ((256, 1), (200, 57), (200, 130))
+PADDED_RATES = (0, 5, 65)
+PADDED_N, PADDED_WINDOW = 400, "100-102"
+
+
+def shape_graph(lengths, seed, pools=None):
+    """A CSR matrix whose row i has lengths[i] distinct ascending columns other than i, drawn from pools[i] where that is given
+    and from all vertices otherwise, with float32 values uniform in [0.05, 1] (an entry of value w is due in about w / wmax of
+    the epochs: roughly half of them in any one).  Not symmetric: the layout reads rows only."""
+    rng = np.random.default_rng(seed)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    N = len(lengths)
+    cols = []
+    for i, n in enumerate(lengths):
+        pool = np.setdiff1d(np.arange(N) if pools is None or i not in pools else pools[i], [i])
+        cols.append(np.sort(rng.choice(pool, size=int(n), replace=False)))
+    indices = np.concatenate(cols).astype(np.int32)
+    data = rng.uniform(0.05, 1.0, size=len(indices)).astype(np.float32)
+    indptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    return sp.csr_matrix((data, indices, indptr), shape=(N, N))
+
+
+@functools.lru_cache(maxsize=None)
+def seams():
+    """(P, Y0), 300 vertices.  Rows 0 .. 19 have the lengths SEAM_LENGTHS: empty, shorter than, as long as and longer than one
+    and two rounds of a group, both sides of the hub threshold, every other vertex; the rest 0 .. 19 entries.  Y0 is uniform in
+    [-10, 10] except for the 30 vertices of SEAM_SHARED, which start at one position and whose rows name each other only: their
+    attractions run at d2 == 0 and leave them in place, so that a negative sample among them is a repulsion at d2 == 0."""
+    rng = np.random.default_rng(101)
+    N = 300
+    lengths = np.concatenate([SEAM_LENGTHS, rng.integers(0, 20, size=N - len(SEAM_LENGTHS))])
+    shared = np.arange(N)[SEAM_SHARED]
+    P = shape_graph(lengths, 102, pools={int(v): shared for v in shared})
+    # the last entry of the row of 257 is alone in the fifth round of its wave; at the smallest value it is due in epochs 19,
+    # 39, .., 99, 119 only, so in the tested epochs the wave path meets a round with nothing due (64 entries never all rest)
+    P.data[P.indptr[SEAM_LENGTHS.index(257) + 1] - 1] = 0.05
+    Y0 = rng.uniform(-10.0, 10.0, size=(N, 2))
+    Y0[SEAM_SHARED] = Y0[SEAM_SHARED.start]
+    return P, Y0
+
+
+@functools.lru_cache(maxsize=None)
+def many_hubs():
+    """(P, Y0), 1 100 vertices: 1 030 rows of 257 + (h mod 44) entries, h the hub's ordinal, and 70 rows of 0 .. 19 entries spread
+    among them: more hubs than HUB_WAVES, so the stride loop over the hub list makes a second round."""
+    rng = np.random.default_rng(201)
+    N = 1100
+    short = np.linspace(0, N - 1, 70).astype(np.int64)
+    lengths = np.zeros(N, dtype=np.int64)
+    is_hub = np.ones(N, dtype=bool)
+    is_hub[short] = False
+    lengths[is_hub] = 257 + np.arange(is_hub.sum()) % 44
+    lengths[short] = rng.integers(0, 20, size=len(short))
+    return shape_graph(lengths, 202), rng.uniform(-10.0, 10.0, size=(N, 2))
+
+
+@functools.lru_cache(maxsize=None)
+def padded(L, pad):
+    """(P, Y0, v), PADDED_N vertices: rows of 0 .. 19 entries, and the last row v with L entries at columns below PADDED_N - 131
+    followed by ``pad`` entries of value PAD_VALUE at the columns from there on.  The padding has schedule word 0, is never due,
+    and, coming last in the last row, shifts no entry index: padded(L, pad) and padded(L, 0) differ in the length of row v only."""
+    N = PADDED_N
+    v, first_pad = N - 1, N - 131
+    assert 0 <= pad <= v - first_pad and 0 < L <= first_pad
+    rng = np.random.default_rng(301)
+    lengths = np.concatenate([rng.integers(0, 20, size=N - 1), [0]])
+    base = shape_graph(lengths, 302)
+    Y0 = rng.uniform(-10.0, 10.0, size=(N, 2))
+    row = np.random.default_rng(303 + L)
+    cols = np.concatenate([np.sort(row.choice(first_pad, size=L, replace=False)), first_pad + np.arange(pad)])
+    vals = np.concatenate([row.uniform(0.05, 1.0, size=L), np.full(pad, PAD_VALUE)])
+    indptr = base.indptr.astype(np.int64).copy()
+    indptr[-1] += L + pad
+    P = sp.csr_matrix((np.concatenate([base.data, vals]).astype(np.float32), np.concatenate([base.indices, cols]).astype(np.int32), indptr),
+                      shape=(N, N))
+    return P, Y0, v
+
+
+def exact_graph(name):
+    if name == "seams":
+        return seams()
+    if name == "many_hubs":
+        return many_hubs()
+    return crafted() if name == "crafted" else layout_graph(name)
+
+
+def exact_cases():
+    """(graph, window, negative_sample_rate), all on the t-UMAP curve with LAYOUT_EPOCHS epochs and LAYOUT_SEED."""
+    cases = [("seams", "100-101", r) for r in SEAM_RATES]
+    cases += [("seams", "0-1", 5), ("seams", "100-103", 5), ("many_hubs", "100-102", 5)]
+    return cases + [(g, r, 5) for g in ("rand", "hub") for r in RANGES] + [("crafted", "100-101", 5)]
+
+
+def exact_id(case):
+    return "-".join(str(c) for c in case)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_port(graph, window, rate, dtype=np.float32):
+    """The port's result of an exact case in ``dtype``; computed once, not to be written to."""
+    P, Y0 = exact_graph(graph)
+    lo, hi = WINDOWS[window]
+    Y = un.layout(P, Y0, LAYOUT_EPOCHS, 1.0, 1.0, 1.0, 1.0, rate, LAYOUT_SEED, lo, hi, dtype)
+    Y.setflags(write=False)
+    return Y
+
+
+def entry_rows(P):
+    """(row, position within the row) of every entry."""
+    length = np.diff(P.indptr)
+    rows = np.repeat(np.arange(P.shape[0]), length)
+    return rows, np.arange(len(rows)) - P.indptr[rows]
+
+
+def round_coverage(P, n):
+    """Per path (GROUP: rows of up to HUB_LEN entries, WAVE: longer ones), what the schedule of epoch n does to the rounds of G
+    entries a row is fetched in: ``first`` / ``last``: a due entry sits in lane slot 0 / G - 1; ``ragged``: a due entry sits in
+    a last round of fewer than G entries; ``empty``: some round has no due entry; ``rows``: the rows on that path."""
+    fire = un.due(un.schedule(P.data), n)
+    length = np.diff(P.indptr)
+    rows, pos = entry_rows(P)
+    out = {}
+    for G, sel in ((GROUP, length[rows] <= HUB_LEN), (WAVE, length[rows] > HUB_LEN)):
+        slot, rnd = pos % G, pos // G
+        in_ragged = rnd == length[rows] // G                     # a last round that is not full (pos < length)
+        rid = rows * (P.shape[0] + 1) + rnd
+        out[G] = dict(first=bool((sel & fire & (slot == 0)).any()), last=bool((sel & fire & (slot == G - 1)).any()),
+                      ragged=bool((sel & fire & in_ragged).any()), empty=len(np.unique(rid[sel & fire])) < len(np.unique(rid[sel])),
+                      rows=int(((length <= HUB_LEN) if G == GROUP else (length > HUB_LEN)).sum()))
+    return out
+
+
+def sample_ids(P, n, rate, seed=LAYOUT_SEED):
+    """(entries due in epoch n, their rows, their negative samples as a len x rate table), by the key of include/gficf_umap.h."""
+    e = np.flatnonzero(un.due(un.schedule(P.data), n))
+    rows, _ = entry_rows(P)
+    N = np.uint64(P.shape[0])
+    with np.errstate(over="ignore"):
+        ke = un.mix(un.mix(np.uint64((int(seed) + n) & 0xFFFFFFFFFFFFFFFF)) + e.astype(np.uint64))
+        jn = [((un.mix(ke + np.uint64(s)) >> np.uint64(32)) * N) >> np.uint64(32) for s in range(rate)]
+    return e, rows[e], np.stack(jn, axis=1).astype(np.int64) if rate else np.zeros((len(e), 0), dtype=np.int64)
+
+
+def self_samples(P, n, rate, seed=LAYOUT_SEED):
+    """How many negative samples of epoch n name their own vertex: the ``jn != v`` skip."""
+    _, rows, jn = sample_ids(P, n, rate, seed)
+    return int((jn == rows[:, None]).sum())
+
+
+def seams_zero_distance(n, rate, seed=LAYOUT_SEED):
+    """(attractions, repulsions) at d2 == 0 that epoch n is certain to hold when it starts from seams()'s Y0: a due entry between
+    two vertices of SEAM_SHARED; and, for such a vertex, a sample among the others of SEAM_SHARED before anything has moved it
+    (every attraction of its row leaves it in place, a sample naming the vertex itself is skipped, any other sample ends the walk)."""
+    P, _ = seams()
+    e, rows, jn = sample_ids(P, n, rate, seed)
+    lo, hi = SEAM_SHARED.start, SEAM_SHARED.stop
+    inside = (rows >= lo) & (rows < hi)
+    assert ((P.indices[e[inside]] >= lo) & (P.indices[e[inside]] < hi)).all()
+    repulsions = 0
+    for v in range(lo, hi):
+        moved = False
+        for t in np.flatnonzero(rows == v):                        # the due entries of row v in row order
+            for j in jn[t]:
+                if j == v:
+                    continue
+                repulsions += lo <= j < hi                         # the first sample that is applied: it moves v either way
+                moved = True
+                break
+            if moved:
+                break
+    return int(inside.sum()), int(repulsions)
+
+
 # ------------------------------------------------------------------------------------------------ quality
 QUALITY_SEEDS = (1, 2, 3, 4, 5)
 QUALITY_EPOCHS = 200
@@ -219,6 +403,11 @@ def _main():
     for case in layout_cases():
         dev = float(np.abs(port_layout(*case, np.float32).astype(np.float64) - port_layout(*case, np.float64)).max())
         print(f"    {case!r}: {dev:.3e},")
+    print("}")
+    print("MEASURED_EXACT = {      # case: (vertices compared, |port f32 - port f64|)")
+    for case in exact_cases():
+        f32 = exact_port(*case, np.float32)
+        print(f"    {case!r}: ({len(f32)}, {float(np.abs(f32.astype(np.float64) - exact_port(*case, np.float64)).max()):.3e}),")
     print("}")
     X, labels, cells = quality_input()
     print("initial plane:", un.quality(X, cells[:, :2], labels))

@@ -113,6 +113,81 @@ def test_crafted_case_takes_the_zero_distance_branch():
     assert hi == lo + 1 and tn.due(tn.row_schedule(W)[tc.CRAFTED, 0], lo).all()     # whose entry is due in the chosen epoch
 
 
+# ------------------------------------------------------------------------------------------------ the exact cases are not vacuous
+@pytest.mark.parametrize("k", tc.EXACT_KS)
+def test_exact_inputs_follow_the_recipe_of_the_rand_case(k):
+    idx, W, Yt, Y0 = tc.layout_case("rand", k)
+    assert idx.shape == W.shape == (500, k) and Yt.shape == (1500, 2) and Y0.shape == (500, 2) and max(tc.EXACT_MS) == 500
+    assert idx.min() >= 1 and idx.max() <= 1500 and W.dtype == Y0.dtype == Yt.dtype == np.float32
+    assert (W >= 0).all() and (W.max(axis=1) > 0).all() and np.isfinite(Y0).all()
+    ref = tc.layout_case("rand")
+    lead = min(k, tc.LAYOUT_K)
+    assert np.array_equal(idx[:, :lead], ref[0][:, :lead]) and np.array_equal(Yt, ref[2])      # the same points, the same plane
+    if k == tc.EXACT_CRAFTED_K:
+        cidx, cW, _, cY0 = tc.layout_case("crafted", k)
+        assert np.array_equal(cidx, idx) and np.array_equal(cW, W)
+        assert np.array_equal(cY0[tc.CRAFTED], Yt[idx[tc.CRAFTED, 0] - 1])          # the cells start on a trained neighbour
+        for n in range(*tc.EXACT_WINDOW):
+            assert tn.due(tn.row_schedule(W)[tc.CRAFTED, 0], n).all()               # whose entry is due in the tested epochs
+
+
+@pytest.mark.parametrize("k", tc.EXACT_KS)
+def test_schedule_reaches_every_kind_of_round(k):
+    """In both tested epochs a due entry sits in the first lane slot of a round; in the last one where a row fills a round
+    (k >= 8); in a ragged last round where there is one (k no multiple of 8).  Some round has nothing due at k = 9, 17 and 128.
+    Up to k = 8 none can: a row's one round holds its largest membership, which is due in every epoch but the first.  At
+    k = 16 none does: no membership of this input is below 0.35 of its row's largest, and eight of them never all rest."""
+    W = tc.layout_case("rand", k)[1]
+    for n in range(*tc.EXACT_WINDOW):
+        c = tc.round_coverage(W, n)
+        assert c["first"] and c["last"] == (k >= tc.GROUP) and c["ragged"] == (k % tc.GROUP != 0), (k, n, c)
+        if k != 16:
+            assert c["empty"] == (k > tc.GROUP), (k, n, c)
+    assert any(tc.round_coverage(tc.layout_case("rand", kk)[1], tc.EXACT_WINDOW[0])["empty"] for kk in tc.EXACT_KS)
+
+
+@pytest.mark.parametrize("case", tc.exact_cases(), ids=lambda c: "-".join(str(v) for v in c))
+def test_exact_cases_tell_float32_from_float64(case):
+    """Equality with the float32 port is a statement the float64 port would fail: the two differ on every case, and every cell
+    moves (its largest membership is due in both epochs; a crafted cell, attracted at d2 == 0, by its other entries or samples)."""
+    name, k, rate = case
+    Y0 = tc.layout_case(name, k)[3]
+    f32, f64 = tc.exact_port(name, k, rate, np.float32), tc.exact_port(name, k, rate, np.float64)
+    dev = float(np.abs(f32.astype(np.float64) - f64).max())
+    print(f"{case}: {len(f32)} cells, |port f32 - port f64| = {dev:.3e}")
+    assert f32.dtype == np.float32 and f32.shape == Y0.shape and np.isfinite(f32).all()
+    assert dev > 0 and not np.array_equal(f32, f64.astype(np.float32))              # not even after rounding
+    moved = (f32 != Y0).any(axis=1)
+    if name == "crafted" and rate == 0:
+        assert moved[:tc.CRAFTED.start].all() and moved[tc.CRAFTED.stop:].all() and moved[tc.CRAFTED].sum() > 40
+    else:
+        assert moved.all()
+
+
+@pytest.mark.parametrize("k", tc.EXACT_KS)
+def test_port_cell_depends_on_its_row_and_offset_only(k):
+    """What lets the GPU tests compare M cells with the first M rows of one run of the port."""
+    idx, W, Yt, Y0 = tc.layout_case("rand", k)
+    whole = tc.exact_port("rand", k, 7)
+    for M in tc.EXACT_MS[:-1]:
+        assert np.array_equal(tn.layout(idx[:M], W[:M], Yt, Y0[:M], tc.LAYOUT_EPOCHS, **tc.exact_kw(7)), whole[:M])
+    first, off = tc.EXACT_OFFSETS[0]
+    assert np.array_equal(tc.exact_port("rand", k, 7, first=first, query_offset=off), whole[first:])
+    first, off = tc.EXACT_OFFSETS[1]
+    assert not np.array_equal(tc.exact_port("rand", k, 7, first=first, query_offset=off), whole)
+
+
+@pytest.mark.parametrize("k", tc.INIT_KS)
+def test_init_case_holds_zero_memberships_and_a_row_of_nothing_else(k):
+    idx, W, Yt = tc.init_case(k)
+    assert idx.shape == W.shape == (300, k) and idx.min() >= 1 and idx.max() <= len(Yt) == 400
+    assert (W[tc.INIT_ZERO_ROW] == 0).all() and (W == 0).sum() > k and (W.sum(axis=1) > 0).sum() >= 250 and W.max() <= 1
+    Y = tn.init_positions(idx, W, Yt)
+    y64 = Yt.astype(np.float64)[idx - 1]
+    assert np.abs(Y[tc.INIT_ZERO_ROW] - y64[tc.INIT_ZERO_ROW].mean(0)).max() <= 2 * (k + 2) * 2.0 ** -24 * 10
+    assert np.isfinite(Y).all()
+
+
 # ------------------------------------------------------------------------------------------------ vote
 def test_vote_tie_rule_on_hand_made_rows():
     labels = np.array([0, 1, 2, 2, 1, 0, 3], dtype=np.int32)                        # training ids 1 .. 7

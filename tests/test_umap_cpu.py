@@ -97,6 +97,125 @@ def test_port_layout_split_equals_whole():
     assert not np.array_equal(whole, np.asarray(Y0, dtype=np.float32))
 
 
+# ------------------------------------------------------------------------------------------------ the exact cases are not vacuous
+def _check_shape_graph(P, lengths):
+    assert P.dtype == np.float32 and np.array_equal(np.diff(P.indptr), lengths)
+    for i in range(P.shape[0]):
+        c = P.indices[P.indptr[i]:P.indptr[i + 1]]
+        assert (np.diff(c) > 0).all() and not (c == i).any() and (len(c) == 0 or (c[0] >= 0 and c[-1] < P.shape[0])), i
+    assert P.data.min() >= np.float32(0.05) and P.data.max() <= 1
+
+
+def test_seams_has_the_row_lengths_it_claims():
+    P, Y0 = uc.seams()
+    length = np.diff(P.indptr)
+    assert P.shape == (300, 300) and Y0.shape == (300, 2) and np.abs(Y0).max() <= 10
+    assert tuple(length[:20]) == uc.SEAM_LENGTHS and length[20:].max() < 20
+    assert {0, 1, 2, 7, 8, 9, 15, 16, 17, 24, 25, 63, 64, 65, 255, 256, 257, 258, 299} <= set(length.tolist())
+    assert (length == 0).sum() >= 2 and (length > uc.HUB_LEN).sum() == 3
+    _check_shape_graph(P, length)
+    shared = np.arange(300)[uc.SEAM_SHARED]
+    assert len(shared) == 30 and len(np.unique(Y0[shared], axis=0)) == 1 and len(np.unique(Y0, axis=0)) == 271
+    for v in shared:                                                                # their rows name each other only
+        assert np.isin(P.indices[P.indptr[v]:P.indptr[v + 1]], shared).all()
+
+
+def test_many_hubs_has_more_hubs_than_hub_waves():
+    P, Y0 = uc.many_hubs()
+    length = np.diff(P.indptr)
+    hubs = length[length > uc.HUB_LEN]
+    assert P.shape == (1100, 1100) and len(hubs) == 1030 > uc.HUB_WAVES and (length <= uc.HUB_LEN).sum() == 70
+    assert np.array_equal(hubs, 257 + np.arange(1030) % 44) and length[length <= uc.HUB_LEN].max() < 20
+    assert 280_000 < P.nnz < 290_000
+    assert P.nnz // uc.HUB_LEN + 1 >= 1030                                          # the hub list of the library holds them all
+    _check_shape_graph(P, length)
+
+
+@pytest.mark.parametrize("L,pad", uc.PADDED)
+def test_padded_differs_from_its_plain_form_in_entries_that_are_never_due(L, pad):
+    P, Y0, v = uc.padded(L, pad)
+    Q, Y0q, vq = uc.padded(L, 0)
+    assert v == vq == P.shape[0] - 1 and np.array_equal(Y0, Y0q)
+    assert np.diff(P.indptr)[v] == L + pad > uc.HUB_LEN >= L == np.diff(Q.indptr)[v]      # the wave path against the group path
+    assert np.diff(P.indptr)[:v].max() < 20
+    n = Q.nnz
+    assert P.nnz == n + pad and np.array_equal(P.indptr[:-1], Q.indptr[:-1])
+    assert np.array_equal(P.indices[:n], Q.indices) and np.array_equal(P.data[:n].view(np.uint32), Q.data.view(np.uint32))
+    assert (P.indices[n:] > P.indices[n - 1]).all() and (np.diff(P.indices[P.indptr[v]:]) > 0).all() and P.indices[-1] < v
+    q = un.schedule(P.data)
+    assert (q[n:] == 0).all() and np.array_equal(q[:n], un.schedule(Q.data))         # the padding: schedule word 0, the rest unchanged
+    lo, hi = uc.WINDOWS[uc.PADDED_WINDOW]
+    for e in range(lo, hi):
+        assert un.due(q[P.indptr[v]:], e).sum() > 20                                # row v has work in every epoch of the window
+
+
+def _windows_of(graph):
+    return sorted({w for g, w, _ in uc.exact_cases() if g == graph})
+
+
+@pytest.mark.parametrize("graph", ["seams", "many_hubs", "rand", "hub"])
+def test_schedule_reaches_every_kind_of_round(graph):
+    """In every epoch of every tested window beyond epoch 0: a due entry in the first and in the last lane slot of a round, one
+    in a ragged last round, and a round without any; on both paths of the crafted graphs, on the group path of the two kNN
+    graphs ("rand" has no hub, and the one hub of "hub" has few due entries: what the crafted graphs are for)."""
+    P, _ = uc.exact_graph(graph)
+    for w in _windows_of(graph):
+        for n in range(*uc.WINDOWS[w]):
+            if n == 0:
+                assert not un.due(un.schedule(P.data), 0).any()
+                continue
+            cov = uc.round_coverage(P, n)
+            for G in (uc.GROUP, uc.WAVE) if graph in ("seams", "many_hubs") else (uc.GROUP,):
+                c = cov[G]
+                assert c["rows"] > 0 and c["first"] and c["last"] and c["ragged"] and c["empty"], (graph, n, G, c)
+
+
+def test_negative_samples_name_their_own_vertex():
+    for graph, w, rate in uc.exact_cases():
+        lo, hi = uc.WINDOWS[w]
+        if graph in ("seams", "many_hubs") and rate >= 5 and lo > 0:
+            P, _ = uc.exact_graph(graph)
+            assert sum(uc.self_samples(P, n, rate) for n in range(lo, hi)) > 0, (graph, w, rate)
+
+
+def test_seams_takes_the_zero_distance_branches_of_both_forces():
+    for n in (100,):                                                                # the first epoch of both windows beyond epoch 0
+        for rate in uc.SEAM_RATES:
+            attractions, repulsions = uc.seams_zero_distance(n, rate)
+            assert attractions >= 2 and (repulsions >= 1 or rate == 0), (rate, attractions, repulsions)
+
+
+@pytest.mark.parametrize("case", uc.exact_cases(), ids=uc.exact_id)
+def test_exact_cases_tell_float32_from_float64(case):
+    """Equality with the float32 port is a statement the float64 port would fail: the two differ on every case, the sweep moves
+    every vertex with a due entry towards a vertex that is somewhere else, and leaves every vertex without a due entry alone."""
+    graph, w, rate = case
+    P, Y0 = uc.exact_graph(graph)
+    f32, f64 = uc.exact_port(graph, w, rate, np.float32), uc.exact_port(graph, w, rate, np.float64)
+    start = np.asarray(Y0, dtype=np.float32)
+    dev = float(np.abs(f32.astype(np.float64) - f64).max())
+    print(f"{uc.exact_id(case)}: {len(f32)} vertices, |port f32 - port f64| = {dev:.3e}")
+    assert f32.dtype == np.float32 and f32.shape == start.shape and np.isfinite(f32).all()
+    lo, hi = uc.WINDOWS[w]
+    q = un.schedule(P.data)
+    rows, _ = uc.entry_rows(P)
+    fire = np.zeros(P.nnz, dtype=bool)
+    for n in range(lo, hi):
+        fire |= un.due(q, n)
+    idle = np.ones(len(start), dtype=bool)
+    idle[rows[fire]] = False
+    apart = fire & (start[rows] != start[P.indices]).any(axis=1)
+    busy = np.zeros(len(start), dtype=bool)
+    busy[rows[apart]] = True
+    moved = (f32 != start).any(axis=1)
+    assert not moved[idle].any() and moved[busy].all()
+    if hi == 1:
+        assert not fire.any() and np.array_equal(f32, start)                        # epoch 0: nothing is due, nothing to tell apart
+    else:
+        assert busy.sum() > len(start) // 2 and dev > 0
+        assert not np.array_equal(f32, f64.astype(np.float32))                      # not even after rounding
+
+
 # ------------------------------------------------------------------------------------------------ the mirror's argument handling
 def _data(n=40, dim=5):
     return {"pca": {"cells": np.random.default_rng(1).standard_normal((n, dim))}}
