@@ -12,7 +12,9 @@
 //   per block        k_sp_mul<b>                       W = S V_j, from the pre-scaled block Xs = D^-1/2 V_j
 //                    2 x (k_sp_proj_part, k_sp_proj_fin, k_sp_axpy<b>)   c = [q0 V]' W over the chunks, their sum in order, W -= [q0 V] c
 //                    2 x (k_sp_proj_part, k_sp_chol, k_sp_apply<b>)      G = W' W, the b x b kernel, W <- W T; the second writes V_{j+1} and Xs
-//   per restart      k_sp_rotate (V <- V Z), k_sp_apply<b> (the residual block W_last Z_last)
+//   per cycle        blocks until the next would not fit: capped by m the cycle ends at its last FULL block (me <= mc columns, no column
+//                    of a remainder discarded), capped by N - 1 the last block is as narrow as what is left; G_last = W_last' W_last
+//   per restart      k_sp_rotate (V <- V Z, over the me columns of the cycle; Z: the kept Ritz vectors, chosen on the host), k_sp_apply<b> (the residual block W_last Z_last)
 //   at the end       k_sp_rotate, k_sp_amax_part / k_sp_sign_fin / k_sp_flip (the sign rule), k_sp_scale, k_sp_mul<b>, k_sp_resid<b>, the norms
 // What bounds a block step at 54 000 vertices: P (12 B an entry) and V (N x m f64) both stay in the L2 / the infinity cache, the
 // kernels are short, so the step is about thirteen launch latencies.
@@ -561,6 +563,7 @@ int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, 
              double tol, int m, int max_restarts, double* d_theta, double* d_resid, double* d_X, int64_t* h_info) {
   hipStream_t st = ctx->stream;
   const int mc = (int64_t)m < N - 1 ? m : (int)(N - 1), ldv = m, ldh = w.ldh;
+  const bool capped = (int64_t)mc < N - 1;                      // by m, not by the complement of q0
   const dim3 rows(sp_grid(N)), one(1), red(SP_RED);
   const size_t blk = sizeof(double) * (size_t)N * (size_t)b;
   const double eps23 = std::pow(2.0, -52.0 * 2.0 / 3.0);
@@ -611,28 +614,29 @@ int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, 
   std::vector<int32_t> hflags((size_t)m);
   std::vector<double> theta((size_t)b, 0.0), resid((size_t)b, 0.0);
   for (;;) {
-    // ---- one cycle: the basis grown to mc columns, then the remainder of the last block and its Gram matrix
+    // ---- one cycle: the basis grown to mc columns (capped by m: to its last full block), then the remainder of the last block and its Gram matrix
     for (;;) {
       mul(w.Xs, w.W);
       project(nc, c0);
-      if (nc == mc) break;
+      if (nc == mc || (capped && mc - nc < b)) break;           // capped by m: no narrower block, no column of a remainder is discarded
       const int bwn = b < mc - nc ? b : mc - nc;
       orth(nc, bwn);
       c0 = nc; bw = bwn; nc += bwn;
     }
+    const int me = nc;                                          // the columns this cycle ended with
     hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.W, b, b, (const double*)nullptr, (const double*)w.W, b, N, w.parts);
     hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, b * b, w.G, (double*)nullptr, 0, 0, b, (double*)nullptr, 0);
     GFICF_HIP_CHECK(hipGetLastError());
     uint32_t hst = 0;
-    GFICF_HIP_CHECK(hipMemcpyAsync(hH.data(), w.H, sizeof(double) * (size_t)ldh * (size_t)mc, hipMemcpyDeviceToHost, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(hH.data(), w.H, sizeof(double) * (size_t)ldh * (size_t)me, hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipMemcpyAsync(hG.data(), w.G, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToHost, st));
-    GFICF_HIP_CHECK(hipMemcpyAsync(hflags.data(), w.flags, sizeof(int32_t) * (size_t)mc, hipMemcpyDeviceToHost, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(hflags.data(), w.flags, sizeof(int32_t) * (size_t)me, hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipMemcpyAsync(&hst, w.cc.status, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipStreamSynchronize(st));
     if (hst & SP_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "a value of the graph that is not positive and finite");
     // ---- Rayleigh-Ritz on the live columns
     std::vector<int> live;
-    for (int j = 0; j < mc; ++j)
+    for (int j = 0; j < me; ++j)
       if (j < keep || hflags[(size_t)j]) live.push_back(j);
     const int n = (int)live.size();
     if (n < b) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "the start block spans %d directions outside the trivial eigenvector, ndim = %d asked for", n, b);
@@ -644,27 +648,27 @@ int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, 
         A[(size_t)x * n + y] = A[(size_t)y * n + x] = h;
       }
     sp_jacobi(A, n, ev, Z);
-    Zfull.assign((size_t)mc * n, 0.0);
+    Zfull.assign((size_t)me * n, 0.0);
     for (int x = 0; x < n; ++x)
       for (int l = 0; l < n; ++l) Zfull[(size_t)live[(size_t)x] * n + l] = Z[(size_t)x * n + l];
     bool pass = true;
     for (int l = 0; l < b; ++l) {
       double s = 0.0;
       for (int x = 0; x < bw; ++x)
-        for (int y = 0; y < bw; ++y) s += Zfull[(size_t)(mc - bw + x) * n + l] * hG[(size_t)x * b + y] * Zfull[(size_t)(mc - bw + y) * n + l];
+        for (int y = 0; y < bw; ++y) s += Zfull[(size_t)(me - bw + x) * n + l] * hG[(size_t)x * b + y] * Zfull[(size_t)(me - bw + y) * n + l];
       theta[(size_t)l] = ev[(size_t)l];
       pass = pass && std::sqrt(s > 0.0 ? s : 0.0) <= tol * std::max(std::fabs(ev[(size_t)l]), eps23);
     }
     const int kp = std::min(b + 2, n);
-    const bool can_restart = restarts < max_restarts && kp < mc;
+    const bool can_restart = restarts < max_restarts && kp < me;
     if (pass || !can_restart) {
       // ---- X = V Z[:, :b], signed; the residuals recomputed from one more multiplication
-      up.assign((size_t)mc * b, 0.0);
-      for (int j = 0; j < mc; ++j)
+      up.assign((size_t)me * b, 0.0);
+      for (int j = 0; j < me; ++j)
         for (int l = 0; l < b; ++l) up[(size_t)j * b + l] = Zfull[(size_t)j * n + l];
       GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, st));
       GFICF_HIP_CHECK(hipMemcpyAsync(w.theta, theta.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * b)), dim3(256), 0, st, (const double*)V, ldv, mc, (const double*)w.Z, b, d_X, b, N);
+      hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * b)), dim3(256), 0, st, (const double*)V, ldv, me, (const double*)w.Z, b, d_X, b, N);
       hipLaunchKernelGGL(k_sp_amax_part, red, dim3(64), 0, st, (const double*)d_X, b, N, w.pv, w.pi);
       hipLaunchKernelGGL(k_sp_sign_fin, one, dim3(64), 0, st, (const double*)d_X, b, (const double*)w.pv, (const int64_t*)w.pi, w.sign);
       hipLaunchKernelGGL(k_sp_flip_scale, dim3(sp_grid(N * b)), dim3(256), 0, st, d_X, b, N, (const double*)w.sign, (const double*)w.dis, w.Xfs);
@@ -685,19 +689,39 @@ int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, 
     }
     // ---- thick restart: the leading kp Ritz vectors, then the residuals of the leading b as the next block
     ++restarts;
-    up.assign((size_t)mc * kp, 0.0);
-    for (int j = 0; j < mc; ++j)
-      for (int l = 0; l < kp; ++l) up[(size_t)j * kp + l] = Zfull[(size_t)j * n + l];
+    std::vector<int> sel((size_t)kp);
+    for (int l = 0; l < kp; ++l) sel[(size_t)l] = l;
+    if (keep > 0 && n > kp && mc - kp < 2 * b) {
+      // one block per restarted cycle: the extra kept vectors are the Ritz vectors that carry most of the last leading b (rows < b of Z)
+      std::vector<double> carried((size_t)n, -1.0);
+      for (int l = b; l < n; ++l) {
+        double s = 0.0;
+        for (int i = 0; i < b; ++i) s += Zfull[(size_t)i * n + l] * Zfull[(size_t)i * n + l];
+        carried[(size_t)l] = s;
+      }
+      for (int x = b; x < kp; ++x) {
+        int at = -1;
+        for (int l = b; l < n; ++l)
+          if (carried[(size_t)l] >= 0.0 && (at < 0 || carried[(size_t)l] > carried[(size_t)at])) at = l;   // strict: the lowest index on ties
+        sel[(size_t)x] = at;
+        carried[(size_t)at] = -1.0;
+      }
+      std::sort(sel.begin() + b, sel.end());
+    }
+    up.assign((size_t)me * kp, 0.0);
+    for (int j = 0; j < me; ++j)
+      for (int l = 0; l < kp; ++l) up[(size_t)j * kp + l] = Zfull[(size_t)j * n + sel[(size_t)l]];
     GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, st));
     zl.assign((size_t)b * b, 0.0);
     for (int x = 0; x < bw; ++x)
-      for (int l = 0; l < b; ++l) zl[(size_t)x * b + l] = Zfull[(size_t)(mc - bw + x) * n + l];
+      for (int l = 0; l < b; ++l) zl[(size_t)x * b + l] = Zfull[(size_t)(me - bw + x) * n + l];
     GFICF_HIP_CHECK(hipMemcpyAsync(w.Zl, zl.data(), sizeof(double) * zl.size(), hipMemcpyHostToDevice, st));   // (up, zl: untouched until the next synchronisation)
-    hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * kp)), dim3(256), 0, st, (const double*)V, ldv, mc, (const double*)w.Z, kp, Vo, ldv, N);
+    hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * kp)), dim3(256), 0, st, (const double*)V, ldv, me, (const double*)w.Z, kp, Vo, ldv, N);
     std::swap(V, Vo);
     SP_DISPATCH(b, k_sp_apply, rows, w.W, (const double*)w.Zl, N, (double*)nullptr, ldv, 0, 0, w.Xs, (const double*)w.dis);
     keep = kp;
-    kept.assign(ev.begin(), ev.begin() + kp);
+    kept.assign((size_t)kp, 0.0);
+    for (int l = 0; l < kp; ++l) kept[(size_t)l] = ev[(size_t)sel[(size_t)l]];
     project(keep, -1);
     bw = b < mc - keep ? b : mc - keep;
     orth(keep, bw);

@@ -29,16 +29,31 @@
  *      block   W = S V_j for the newest block V_j; W is projected against q0 and every column of V, TWICE (c = [q0 V]' W,
  *              W -= [q0 V] c); the sums of the two coefficient sets are column block j of H = V' S V (its other triangle is
  *              taken by symmetry); then W is orthonormalised within itself, twice, through its b x b Gram matrix (G = W' W,
- *              Gram-Schmidt in the G inner product in a one-lane kernel, W <- W T) and becomes V_{j+1}.  The last block may be
- *              narrower than b.  A column whose squared norm after the projection is <= 1e-24 x the one before it, or whose
- *              pivot is <= 1e-12 x its own squared norm, is DROPPED (a zero column, flagged): the Krylov space is exhausted
- *              there.  Dropped columns are left out of H on the host.
- *      cycle   ends when V is full.  The remainder W_last of the last block (projected, not normalised) stays, with its Gram
+ *              Gram-Schmidt in the G inner product in a one-lane kernel, W <- W T) and becomes V_{j+1}.  A block is narrower
+ *              than b only where the basis is capped by N - 1 (see cycle).  A column whose squared norm after the projection is
+ *              <= 1e-24 x the one before it, or whose pivot is <= 1e-12 x its own squared norm, is DROPPED (a zero column,
+ *              flagged): the Krylov space is exhausted there.  Dropped columns are left out of H on the host.
+ *      cycle   ends when no further block fits.  Capped by m (mc = m < N - 1): at the last FULL block, so a cycle holds me <= mc
+ *              columns, me = keep + b floor((mc - keep) / b) (keep = 0 in the first), and the columns past me stay unused: no
+ *              column of a remainder is ever discarded, S V - V H stays confined to W_last, and the estimate and the restart
+ *              block below are the true residuals.  (A narrower last block there discards b - bw columns of the remainder
+ *              before it; the estimate is then too small and the iteration stalls: at ndim 3, m 32 at a relative residual
+ *              of 9e-3.)  Capped by N - 1 (mc = N - 1 <= m): the last block takes the mc - nc < b columns that are left; the
+ *              complement of q0 is exhausted, the columns left out are dependent, me = mc.  For ndim 1, and for ndim 2 with an
+ *              even m, me = mc in every cycle.  Everything below reads me for the number of columns.
+ *              The remainder W_last of the last block (projected, not normalised) stays, with its Gram
  *              matrix G_last.  ONE synchronisation per cycle: H, the flags and G_last are read back (8 KB + 0.8 KB at m = 32).
  *              The host solves H = Z diag(theta) Z' (cyclic Jacobi, fixed sweep order, theta descending).  The residual of
  *              Ritz pair l is W_last z_l (z_l: the rows of Z of the last block), its norm sqrt(z_l' G_last z_l).
  *      restart V <- V Z[:, :keep], keep = ndim + 2 (fewer if fewer columns live); the next block is the residuals
- *              W_last Z_last[:, :b] of the leading b pairs, projected and orthonormalised as above.
+ *              W_last Z_last[:, :b] of the leading b pairs, projected and orthonormalised as above.  The kept columns are the
+ *              leading keep Ritz vectors, except where a restarted cycle has room for ONE block only (mc - keep < 2 b, as at
+ *              m = 2 ndim + 2): there, from the second restart on, the two beyond the leading b are the Ritz vectors l >= b
+ *              with the largest sum over i < b of Z[i, l]^2 (the lowest l on ties; kept in ascending l), i.e. those that
+ *              carry most of the previous cycle's leading b vectors.  Any set of Ritz vectors keeps S V - V H inside W_last;
+ *              this set keeps the direction of the last step, the locally optimal recurrence of LOBPCG.  With the next
+ *              Ritz pairs instead, a one-block cycle is a gradient step (connected blobs, ndim 3, m 8: 306 restarts, with
+ *              this rule 70).
  *      stop    when the estimate of each of the leading ndim pairs is <= tol max(|theta|, eps^(2/3)) (eps = 2^-52), or after
  *              max_restarts restarts.  Then X = V Z[:, :ndim], each column signed so that its largest-magnitude entry is
  *              positive (lowest index on ties), and the residuals are RECOMPUTED from one more multiplication: the reported

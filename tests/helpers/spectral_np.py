@@ -1,6 +1,8 @@
 """The numpy side of tests/test_spectral_cpu.py and tests/test_spectral_gpu.py: the dense operator S = D^-1/2 P D^-1/2 and its
 ``eigh``, the canonical sign, the ring with its closed form, and the components through scipy relabelled to the smallest id.
-No second copy of the library's block solver: the device is held to defining properties and to ``eigh``.
+The device's vectors and values are held to defining properties and to ``eigh``, never to a second solver.  The numpy statement
+of the block method in tests/helpers/spectral_block_np.py has another role: it bounds CONVERGENCE (a case is solvable by the
+method within max_restarts, and in how many restarts), and checks no vector.
 
 ``python -m tests.helpers.spectral_np`` recomputes, on the CPU and with the port of tests/helpers/umap_np.py alone, the quality
 figures that tests/test_spectral_gpu.py carries (PORT_QUALITY)."""
@@ -92,6 +94,58 @@ def davis_kahan(values, l, residual):
     """The bound residual / gap on the sine between a vector with that residual and eigenvector l of the (descending) spectrum."""
     others = np.delete(values, l)
     return float(residual / np.abs(others - values[l]).min())
+
+
+def outside_cluster(x, theta, w, U, delta):
+    """The norm of the part of x outside the span of the eigenvectors U[:, i] with |w_i - theta| < delta, from the remainder (as
+    ``sine``).  At most residual / delta for ANY delta: with x = sum c_i u_i, |S x - theta x|^2 = sum (w_i - theta)^2 c_i^2
+    >= delta^2 x (the sum of c_i^2 over the eigenvectors outside)."""
+    Uc = U[:, np.abs(np.asarray(w) - theta) < delta]
+    return float(np.linalg.norm(x - Uc @ (Uc.T @ x)))
+
+
+def subspace_sine(X, Ub):
+    """|X - Ub Ub' X|_2, the sine of the largest angle between span(X) and span(Ub) for orthonormal X (from the remainder: it does
+    not bottom out at 1e-8 as ``subspace_gap`` does).  Davis-Kahan: at most ``subspace_bound``."""
+    return float(np.linalg.norm(X - Ub @ (Ub.T @ X), 2))
+
+
+def subspace_bound(w, values, residuals):
+    """|residuals|_2 / sep on ``subspace_sine(X, U[:, 1:b + 1])``, sep = min |theta_l - w_i| over the eigenvalues i that are not
+    among the b leading non-trivial ones (the trivial one included).  With R = S X - X diag(theta) and U2 those eigenvectors,
+    (U2' X)_il = (U2' R)_il / (w_i - theta_l), so |U2' X|_2 <= |U2' X|_F <= |R|_F / sep."""
+    b = len(values)
+    others = np.concatenate([w[:1], w[b + 1:]])
+    sep = np.abs(others[:, None] - np.asarray(values)[None, :]).min()
+    return float(np.linalg.norm(residuals) / sep)
+
+
+# ------------------------------------------------------------------------------------------------ graphs of hubs and of threshold rows
+HUB_LEN = 256                         # SP_HUB_LEN of spectral.hip: a longer row is multiplied by a whole wave from the hub list
+HUB_WAVES = 1024                      # SP_HUB_WAVES: the waves that share the hub list, at most
+
+
+def planted(N=1100, groups=9, seed=4):
+    """The complete graph on N vertices without its diagonal, label = i % groups: weights uniform(0.5, 1) within a group and
+    uniform(0.01, 0.1) across, symmetrised from the upper triangle.  Every row has N - 1 entries: N hub rows, more than the
+    hub waves, and no row for the 8-lane path.  groups - 1 eigenvalues near 0.58, then a gap down to 0.02."""
+    rng = np.random.default_rng(seed)
+    label = np.arange(N) % groups
+    inside, across = rng.uniform(0.5, 1.0, (N, N)), rng.uniform(0.01, 0.1, (N, N))
+    W = np.triu(np.where(label[:, None] == label[None, :], inside, across), 1).astype(np.float32)
+    P = sp.csr_matrix(W + W.T)
+    P.sort_indices()
+    return P
+
+
+def threshold():
+    """ring(600, 128) plus the edge (0, 300) both ways: 598 rows of exactly HUB_LEN entries (the longest the 8-lane path takes) and
+    two of HUB_LEN + 1 (the shortest hubs).  Its spectrum comes in near-degenerate pairs."""
+    P = ring(600, 128).tolil()
+    P[0, 300] = P[300, 0] = 1.0
+    P = P.tocsr().astype(np.float32)
+    P.sort_indices()
+    return P
 
 
 # ------------------------------------------------------------------------------------------------ the connected blobs (case 2)

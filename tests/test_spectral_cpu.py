@@ -11,6 +11,8 @@ import scipy.sparse as sp
 import gficf_amd
 from gficf_amd import _spectral_lib
 from gficf_amd.api import _spectral_args, _spectral_coordinates
+from tests.helpers import spectral_block_np as sb
+from tests.helpers import spectral_cases as sc
 from tests.helpers import spectral_np as sn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -126,3 +128,105 @@ def test_run_reduction_still_refuses_spectral_and_names_the_way():
         gficf_amd.runReduction(data, init="spectral", verbose=False)
     assert "gficf_amd.umap(" in str(e.value) and "spectral_init" in str(e.value)
     assert gficf_amd.api._REDUCTION_KW["init"] == "pca"
+
+
+# ------------------------------------------------------------------------------------------------ the new graphs and bounds
+def test_planted_graph_is_all_hubs_with_a_gap_after_eight():
+    P, w, U, q0, _ = sc.graph("planted")
+    assert P.shape == (1100, 1100) and P.dtype == np.float32 and (P != P.T).nnz == 0 and P.has_sorted_indices
+    assert (np.diff(P.indptr) == 1099).all() and P.diagonal().max() == 0
+    assert (np.diff(P.indptr) > sn.HUB_LEN).sum() > sn.HUB_WAVES                                      # the strided hub loop runs
+    assert abs(w[0] - 1.0) < 1e-12 and 0.5804 - 1e-4 <= w[8] <= w[1] <= 0.5844 + 1e-4
+    assert w[8] - w[9] > 0.56 and abs(w[9] - 0.019) < 1e-3
+
+
+def test_threshold_graph_has_rows_on_both_sides_of_the_hub_length():
+    P, w, U, q0, _ = sc.graph("threshold")
+    n = np.diff(P.indptr)
+    assert P.dtype == np.float32 and (P != P.T).nnz == 0 and P.has_sorted_indices and (P.data == 1).all()
+    assert (n == sn.HUB_LEN).sum() == 598 and np.flatnonzero(n == sn.HUB_LEN + 1).tolist() == [0, 300]
+    assert abs(w[0] - 1.0) < 1e-12
+    assert np.allclose(w[1:5], [0.72331, 0.72326, 0.15847, 0.15845], atol=1e-5)
+    gaps = -np.diff(w[1:7])
+    assert 2e-5 <= gaps[0::2].min() and gaps[0::2].max() < 1e-4 and gaps[1::2].min() > 1e-2           # near-degenerate pairs, the smallest gap 2e-5
+
+
+def test_outside_cluster_and_subspace_sine_meet_their_bounds():
+    P, w, U, q0, S = sc.graph("ring-300-3")
+    rng = np.random.default_rng(0)
+    # a unit vector in the top plane plus a little of everything else: what lies outside the plane obeys residual / delta
+    x = U[:, 1:3] @ np.array([0.6, 0.8]) + 1e-5 * (U @ rng.standard_normal(300))
+    x /= np.linalg.norm(x)
+    theta = float(x @ S @ x)
+    r = float(np.linalg.norm(S @ x - theta * x))
+    outside = np.abs(w - w[1]) > 1e-9
+    assert (~outside).sum() == 2
+    delta = float(np.abs(w[outside] - theta).min())
+    got = sn.outside_cluster(x, theta, w, U, delta)
+    assert 1e-6 < got <= r / delta and got == pytest.approx(np.linalg.norm(np.delete(U, [1, 2], axis=1).T @ x), rel=1e-6)
+    assert sn.outside_cluster(U[:, 1], w[1], w, U, delta) < 1e-14                                     # not 1e-8: from the remainder
+    # a slightly tilted copy of the leading four vectors, each degenerate plane turned within itself
+    turn = np.kron(np.eye(2), np.array([[0.6, -0.8], [0.8, 0.6]]))
+    Q, _ = np.linalg.qr(U[:, 1:5] @ turn + 1e-6 * rng.standard_normal((300, 4)))
+    th = np.diag(Q.T @ S @ Q).copy()
+    res = np.linalg.norm(S @ Q - Q * th[None, :], axis=0)
+    got, bound = sn.subspace_sine(Q, U[:, 1:5]), sn.subspace_bound(w, th, res)
+    assert 1e-7 < got <= bound and bound < 1.0
+    assert got == pytest.approx(np.linalg.norm(np.delete(U, [1, 2, 3, 4], axis=1).T @ Q, 2), rel=1e-6)
+    assert sn.subspace_sine(U[:, 1:5], U[:, 1:5]) < 1e-14
+    sep = min(w[0] - th.max(), th.min() - w[5])
+    assert bound == pytest.approx(np.linalg.norm(res) / sep)
+
+
+# ------------------------------------------------------------------------------------------------ the method in numpy
+@pytest.mark.parametrize("case", sc.MATRIX, ids=sc.case_id)
+def test_block_method_converges_over_the_matrix(case):
+    """Every case of tests/test_spectral_ndim_gpu.py is solvable by the header's method within 200 restarts, to the device's checks."""
+    name, ndim, m, tol = case
+    r = sc.port(name, ndim, m, tol)
+    print(f"{sc.case_id(case)}: {r['restarts']} restarts, {r['multiplications']} multiplications")
+    sc.check_against_eigh(name, r, tol)
+    if name == "ring-300-3":
+        want = [sn.ring_value(300, 3, 1 + l // 2) for l in range(ndim)]
+        assert np.abs(r["values"] - want).max() <= 1e-12
+
+
+@pytest.mark.parametrize("case", sc.SMALL, ids=sc.case_id)
+def test_block_method_on_small_graphs_needs_no_restart(case):
+    """mc = N - 1: the basis spans the whole complement of q0, the narrower last block stays."""
+    name, ndim, m, tol = case
+    r = sc.port(name, ndim, m, tol)
+    sc.check_against_eigh(name, r, tol)
+    assert r["restarts"] == 0 and np.abs(r["values"] - sc.graph(name)[1][1:1 + ndim]).max() <= 1e-12
+
+
+STALLS = [(3, 32), (2, 33)]
+
+
+@pytest.mark.parametrize("ndim,m", STALLS)
+def test_narrow_last_block_stalls(ndim, m):
+    """The rule the header used to state: a cycle capped by m ends in a narrower block.  Not converged after 200 restarts."""
+    r = sc.port("blobs", ndim, m, 1e-4, True)
+    print(f"ndim {ndim}, m {m}: residuals {r['residuals']} after {r['restarts']} restarts")
+    assert not r["converged"] and r["restarts"] == sc.MAX_RESTARTS
+    assert (r["residuals"] > 1e-4 * np.abs(r["values"])).any()
+
+
+@pytest.mark.parametrize("ndim,m", STALLS)
+def test_full_last_block_converges_where_the_narrow_one_stalls(ndim, m):
+    """Why the rule exists: the same two cases, a cycle ended at its last full block (4 and 2 restarts when this was written)."""
+    r = sc.port("blobs", ndim, m, 1e-4)
+    print(f"ndim {ndim}, m {m}: {r['restarts']} restarts")
+    assert r["converged"] and r["restarts"] <= 10
+
+
+def test_block_method_drops_a_duplicated_start_column_and_refuses_q0():
+    P, w, U, q0, S = sc.graph("blobs")
+    g, h = np.random.default_rng(7).standard_normal((2, 1200))
+    for start, most in ((np.stack([g, g], axis=1), 10), (np.stack([g, g, h], axis=1), 12)):
+        r = sc.as_result(sb.solve(P, start.shape[1], start, 1e-4, 32, sc.MAX_RESTARTS))
+        print(f"duplicated column, ndim {start.shape[1]}: {r['restarts']} restarts")
+        sc.check_against_eigh("blobs", r, 1e-4)
+        assert r["restarts"] <= most
+    with pytest.raises(ValueError, match="spans 0 directions"):
+        sb.solve(P, 2, np.stack([q0, -3.0 * q0], axis=1), 1e-4, 32, sc.MAX_RESTARTS)

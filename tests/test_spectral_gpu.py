@@ -22,6 +22,7 @@ import scipy.sparse as sp
 import gficf_amd
 from gficf_amd import GficfError
 from gficf_amd.api import HipOps, umap_init
+from tests.helpers import spectral_cases as sc
 from tests.helpers import spectral_np as sn
 from tests.helpers import umap_cases as uc
 from tests.helpers import umap_np as un
@@ -138,21 +139,7 @@ def test_components_refuse_bad_rows_and_columns():
 
 
 # ------------------------------------------------------------------------------------------------ the properties every solve is held to
-def _check_solution(P, r, tol, w=None, q0=None):
-    V, th = r["vectors"], r["values"]
-    N, b = V.shape
-    if q0 is None:
-        w, _, q0 = sn.spectrum(P)
-    assert r["n_components"] == 1 and r["converged"] and np.isfinite(V).all()
-    assert np.allclose(r["laplacian_values"], 1.0 - th, rtol=0, atol=0)
-    assert (np.diff(th) <= 1e-12).all()
-    res = sn.residuals(P, V, th)
-    print(f"theta {th}, residuals host {res}, device {r['residuals']}, restarts {r['restarts']}, multiplications {r['multiplications']}")
-    assert (res <= tol * np.abs(th) + 1e-12).all()
-    assert np.allclose(r["residuals"], res, rtol=1e-3, atol=1e-13)                 # the reported ones are the true ones
-    assert np.abs(V.T @ q0).max() <= 1e-10 and np.abs(V.T @ V - np.eye(b)).max() <= 1e-10
-    assert np.array_equal(sn.canonical_sign(V), V)
-    return res
+_check_solution = sc.check_solution                            # shared with tests/test_spectral_ndim_gpu.py and the CPU tests
 
 
 # ------------------------------------------------------------------------------------------------ 1. the ring
