@@ -815,7 +815,7 @@ def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = Fa
     conversions).  ``gene_names``: one name per row of ``data["gficf"]``; default ``data["gene_names"]``, else
     ``data["genes"]`` as strings.  Members are matched by name, made unique, unmatched ones dropped, as fgsea does.
     ``convertToEns`` defaults to False here (True in the reference, where it asks biomaRt): the one default that differs.
-    ``nt`` is accepted for signature compatibility.  ``method="GSVA"`` (GSVA / limma) is not provided.
+    ``nt`` is accepted for signature compatibility.  ``method="GSVA"`` (GSVA / limma) is :func:`runGSVA`'s.
 
     ``data["gsea"]`` becomes ``{"pathways", "es", "nes", "pval", "fdr", "stat"}``: the four tables are ``pandas.DataFrame``
     (index: pathway names, columns: ``data["cluster.labels"]``) holding zeros where a pathway was not tested, ``fdr`` is
@@ -830,7 +830,7 @@ def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = Fa
     if method not in ("GSEA", "GSVA"):
         raise ValueError("'method' should be one of \"GSEA\", \"GSVA\"")
     if method == "GSVA":
-        raise NotImplementedError("method=\"GSVA\" (GSVA scores and limma models) is not provided")
+        raise NotImplementedError("method=\"GSVA\" (GSVA scores and limma models) is a function of its own: call runGSVA")
     tsmessage("Choosen method is GSEA...", verbose=verbose)
     if pathways is None:
         if gmt_file is None:
@@ -858,6 +858,276 @@ def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = Fa
     tab = {k: pd.DataFrame(v, index=names, columns=labels) for k, v in (("es", r["es"]), ("nes", r["nes"]), ("pval", r["pval"]), ("fdr", fdr))}
     data["gsea"] = {"pathways": pathways, **tab,
                     "stat": pd.DataFrame({"pathway": [names[i] for i in t], "size": r["size"][t]})}
+    tsmessage("Done!", verbose=verbose)
+    return data
+
+
+# ------------------------------------------------------------------ GSVA and its limma contrasts (libgficf_gsva.so)
+def _gsva_args(M, cluster, ptr, members, min_size, max_size, n_clusters):
+    """What :func:`gsva` and :func:`gsva_scores` decide before the first call into the library: the gene-major CSR (canonical:
+    duplicates summed, columns ascending, stored zeros kept), the int32 cluster ids, C, the pathway CSR and the size bounds."""
+    import scipy.sparse as sp
+
+    M = sp.csr_matrix(M)
+    if M.dtype != np.float64:
+        M = M.astype(np.float64)
+    if not M.has_canonical_format:
+        M = M.copy()
+        M.sum_duplicates()
+    G, N = M.shape
+    if G < 1 or N < 1:
+        raise ValueError("gficf must be a genes x cells matrix with at least one gene and one cell")
+    cl = np.asarray(cluster)
+    if cl.shape != (N,) or not np.issubdtype(cl.dtype, np.integer):
+        raise ValueError("cluster must hold one integer id per cell")
+    cl = np.ascontiguousarray(cl, dtype=np.int32)
+    C = int(n_clusters) if n_clusters is not None else max(int(cl.max()) + 1, 1)
+    if C < 1:
+        raise ValueError("n_clusters must be at least 1")
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+    members = np.ascontiguousarray(members, dtype=np.int32)
+    if ptr.ndim != 1 or len(ptr) < 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or members.ndim != 1 or ptr[-1] != len(members):
+        raise ValueError("ptr must hold P + 1 non-decreasing offsets from 0 to len(members)")
+    if min_size != min_size or max_size != max_size:
+        raise ValueError("min_size and max_size must not be NaN")
+    lo, hi = int(max(min_size, 1)), int(min(max_size, G))
+    return M, cl, C, ptr, members, lo, hi
+
+
+def _gsva_cell_major(rows, cols, N: int):
+    """The cell-major form of entries given gene-major (``rows`` ascending): (colptr, row, src) with ``src`` the index of
+    each entry in the gene-major arrays."""
+    src = np.lexsort((rows, cols)).astype(np.int64)
+    colptr = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols, minlength=N), out=colptr[1:])
+    return colptr, np.ascontiguousarray(rows[src], dtype=np.int32), src
+
+
+def _gsva_forms(M, cl, C: int):
+    """The two sparse forms include/gficf_gsva.h asks for, from the canonical gene-major CSR ``M`` and the cluster ids: the
+    entries grouped by (gene, cluster) (seg_ptr, cell, x; ``perm`` maps a grouped position to its CSR position) and the same
+    entries cell-major (colptr, row, src)."""
+    G, N = M.shape
+    rows = np.repeat(np.arange(G, dtype=np.int64), np.diff(M.indptr))
+    cols = M.indices.astype(np.int64)
+    seg = rows * C + np.clip(cl[cols], 0, C - 1)            # an id out of range is the library's to reject
+    perm = np.argsort(seg, kind="stable")                    # cells stay ascending within a segment
+    seg_ptr = np.zeros(G * C + 1, dtype=np.int64)
+    np.cumsum(np.bincount(seg, minlength=G * C), out=seg_ptr[1:])
+    cell = np.ascontiguousarray(cols[perm], dtype=np.int32)
+    x = np.ascontiguousarray(M.data[perm], dtype=np.float64)
+    colptr, row, src = _gsva_cell_major(rows[perm], cols[perm], N)
+    return seg_ptr, cell, x, perm, colptr, row, src
+
+
+def _gsva_out(es, tested, ssum, ssq):
+    """The outputs both host entries share, from their column-major arrays."""
+    return {"es": es.T, "tested": tested.T.astype(bool), "sum": ssum.T, "sumsq": ssq.T}
+
+
+def gsva(gficf, cluster, ptr, members, min_size=1, max_size=np.inf, ret_stages: bool = False, n_clusters=None, ctx: Context | None = None) -> dict:
+    """GSVA scores of every cell within its cluster (``GSVA::gsva(gficf[, cells], pathways, kcdf="Gaussian", method="gsva")``
+    of the reference's ``runGSEA(method="GSVA")``, R/pathwayAnalisys.R:113) for all clusters in one device call, under the
+    contract of include/gficf_gsva.h: the Gaussian kernel CDF is evaluated exactly, not from GSVA's table.
+
+    ``gficf``: genes x cells (scipy sparse, stored zeros allowed); ``cluster``: one integer id in ``[0, C)`` per cell
+    (``n_clusters``: C, default ``max + 1``); pathways in CSR form (``ptr``: P + 1 offsets, ``members``: rows).
+
+    Returns ``es`` (P x N; zeros where a pathway is not tested in the cell's cluster), ``tested`` (P x C), ``kept`` (G x C: the
+    genes that pass GSVA's constant-gene filter in the cluster), ``sum`` and ``sumsq`` (P x C: the sums of ``es`` and of its
+    squares over each cluster's cells, computed on the device for :func:`gsva_de_pathways`).  With ``ret_stages`` also ``sd``,
+    ``d0`` (G x C) and ``d_nz``, the density of every stored entry in the CSR order of ``scipy.sparse.csr_matrix(gficf)``."""
+    from . import _gsva_lib
+
+    M, cl, C, ptr, members, lo, hi = _gsva_args(gficf, cluster, ptr, members, min_size, max_size, n_clusters)
+    G, N = M.shape
+    P = len(ptr) - 1
+    seg_ptr, cell, x, perm, colptr, row, src = _gsva_forms(M, cl, C)
+    es = np.zeros((N, P), dtype=np.float64)                  # C-order (N, P) == column-major P x N
+    tested = np.zeros((C, P), dtype=np.int32)
+    ssum, ssq = np.zeros((C, P), dtype=np.float64), np.zeros((C, P), dtype=np.float64)
+    kept = np.zeros((C, G), dtype=np.int32)
+    sd, d0 = np.zeros((C, G), dtype=np.float64), np.zeros((C, G), dtype=np.float64)
+    dnz = np.zeros(max(len(x), 1), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_gsva_lib.load().gficf_gsva_host(ctx.handle, G, N, C, _np_ptr(cl), _np_ptr(seg_ptr), _np_ptr(cell), _np_ptr(x), _np_ptr(colptr), _np_ptr(row),
+                                           _np_ptr(src), P, _np_ptr(ptr), _np_ptr(members), lo, hi, _np_ptr(es), _np_ptr(tested), _np_ptr(kept),
+                                           _np_ptr(sd), _np_ptr(d0), _np_ptr(dnz), _np_ptr(ssum), _np_ptr(ssq)))
+    out = _gsva_out(es, tested, ssum, ssq)
+    out["kept"] = kept.T.astype(bool)
+    if ret_stages:
+        d_csr = np.zeros(len(x), dtype=np.float64)
+        d_csr[perm] = dnz[:len(x)]
+        out.update(sd=sd.T, d0=d0.T, d_nz=d_csr)
+    return out
+
+
+def gsva_scores(d_nz, d0, kept, gficf_pattern, cluster, ptr, members, min_size=1, max_size=np.inf, n_clusters=None,
+                ctx: Context | None = None) -> dict:
+    """Stages 3-5 of :func:`gsva` alone, from given densities: the order of every cell's genes, the tested pathways and the
+    scores.  ``d_nz``: one density per stored entry of ``gficf_pattern`` (genes x cells; only its pattern is read) in its CSR
+    order; ``d0`` (G x C): the density of a gene's zeros in a cluster; ``kept`` (G x C).  Returns ``es``, ``tested``, ``sum``,
+    ``sumsq`` as :func:`gsva` does."""
+    from . import _gsva_lib
+
+    M, cl, C, ptr, members, lo, hi = _gsva_args(gficf_pattern, cluster, ptr, members, min_size, max_size, n_clusters)
+    G, N = M.shape
+    P = len(ptr) - 1
+    dnz = np.ascontiguousarray(d_nz, dtype=np.float64)
+    d0 = np.asarray(d0, dtype=np.float64)
+    kept = np.asarray(kept)
+    if dnz.shape != (M.nnz,) or d0.shape != (G, C) or kept.shape != (G, C):
+        raise ValueError("d_nz must hold one density per stored entry, d0 and kept must be G x C")
+    d0 = np.ascontiguousarray(d0.T)                          # C-order (C, G) == column-major G x C
+    kept = np.ascontiguousarray(kept.T != 0, dtype=np.int32)
+    rows = np.repeat(np.arange(G, dtype=np.int64), np.diff(M.indptr))
+    colptr, row, src = _gsva_cell_major(rows, M.indices.astype(np.int64), N)
+    if len(dnz) == 0:
+        dnz = np.zeros(1, dtype=np.float64)
+    es = np.zeros((N, P), dtype=np.float64)
+    tested = np.zeros((C, P), dtype=np.int32)
+    ssum, ssq = np.zeros((C, P), dtype=np.float64), np.zeros((C, P), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_gsva_lib.load().gficf_gsva_scores_host(ctx.handle, G, N, C, _np_ptr(cl), _np_ptr(colptr), _np_ptr(row), _np_ptr(src), M.nnz, _np_ptr(dnz),
+                                                  _np_ptr(d0), _np_ptr(kept), P, _np_ptr(ptr), _np_ptr(members), lo, hi, _np_ptr(es), _np_ptr(tested),
+                                                  _np_ptr(ssum), _np_ptr(ssq)))
+    return _gsva_out(es, tested, ssum, ssq)
+
+
+def _trigamma_inverse(x: float) -> float:
+    """The y with ``trigamma(y) = x`` by Newton's iteration on ``1 / trigamma`` (limma's ``trigammaInverse``)."""
+    from scipy.special import polygamma
+
+    if x > 1e7:
+        return 1.0 / np.sqrt(x)
+    if x < 1e-6:
+        return 1.0 / x
+    y = 0.5 + 1.0 / x
+    for _ in range(50):
+        tri = float(polygamma(1, y))
+        dif = tri * (1.0 - tri / x) / float(polygamma(2, y))
+        y += dif
+        if -dif / y < 1e-8:
+            break
+    return y
+
+
+def _squeeze_var(s2: np.ndarray, df: float):
+    """limma's ``squeezeVar`` in the plain form (no covariate, not robust): the prior ``(s0², df0)`` by ``fitFDist``'s moments
+    of ``log s²`` and the posterior variances."""
+    from scipy.special import digamma, polygamma
+
+    n = len(s2)
+    if n == 1:
+        return s2.copy(), float(s2[0]), 0.0
+    v = np.maximum(s2, 0.0)
+    m = np.median(v)
+    if m == 0:
+        m = 1.0
+    v = np.maximum(v, 1e-5 * m)
+    e = np.log(v) - digamma(df / 2.0) + np.log(df / 2.0)
+    emean = e.mean()
+    evar = ((e - emean) ** 2).sum() / (n - 1) - float(polygamma(1, df / 2.0))
+    if evar > 0:
+        df0 = 2.0 * _trigamma_inverse(float(evar))
+        s02 = float(np.exp(emean + digamma(df0 / 2.0) - np.log(df0 / 2.0)))
+        return (df * s2 + df0 * s02) / (df + df0), s02, df0
+    s02 = float(v.mean())
+    return np.full(n, s02), s02, np.inf
+
+
+def gsva_de_pathways(res: dict, cluster, labels=None, names=None, cluster_minus_other: bool = False):
+    """The limma step of the reference's ``runGSEA(method="GSVA")`` (R/pathwayAnalisys.R:118-136) from what :func:`gsva`
+    returned: for every cluster, ``lmFit`` of the scores on cluster-against-the-rest, ``eBayes`` and ``topTable``, finished on
+    the host in float64 from the per-cluster sums the device computed (``res["sum"]``, ``res["sumsq"]``).
+
+    Rows: the pathways whose scores are not all zero (a positive sum of squares; a pathway with a NaN score, W = 0 in the
+    header, has no finite sums and is left out).  Returns a DataFrame ``logFC, AveExpr,
+    t, P.Value, adj.P.Val, pathway, cluster``, the clusters in id order (``labels[c]`` names cluster c, ``names[p]`` pathway p),
+    each cluster's rows by decreasing ``|t|`` (topTable's order by ``B``, which is monotone in ``t²`` here).  ``logFC`` is
+    mean(other) - mean(cluster), the sign the reference's ``model.matrix(~ factor(clusters))`` gives its ``C<label>vsOTHER``
+    coefficient (the level ``C<label>`` sorts before ``other``); ``cluster_minus_other=True`` flips it (and ``t``).  ``eBayes`` is
+    the non-robust form without trend; the ``B`` column (limma's ``tmixture`` prior) is not provided."""
+    import pandas as pd
+    from scipy import stats
+
+    if not isinstance(res, dict) or "sum" not in res or "sumsq" not in res:
+        raise ValueError("res must be what gsva() or gsva_scores() returned (the device's sums are read from it)")
+    S, Q = np.asarray(res["sum"], dtype=np.float64), np.asarray(res["sumsq"], dtype=np.float64)
+    P, C = S.shape
+    cl = np.asarray(cluster)
+    n1 = np.bincount(cl, minlength=C).astype(np.float64)
+    N = float(len(cl))
+    use = np.flatnonzero(Q.sum(axis=1) > 0)
+    labels = list(range(C)) if labels is None else list(labels)
+    names = np.arange(P) if names is None else np.asarray(names)
+    cols = ["logFC", "AveExpr", "t", "P.Value", "adj.P.Val", "pathway", "cluster"]
+    if len(use) == 0 or N < 3:
+        return pd.DataFrame({k: [] for k in cols})
+    St, Qt = S[use].sum(axis=1), Q[use].sum(axis=1)
+    parts = []
+    df = N - 2.0
+    for c in range(C):
+        a, b = n1[c], N - n1[c]
+        if a < 1 or b < 1:
+            continue
+        S1, S2 = S[use, c], St - S[use, c]
+        rss = np.maximum((Q[use, c] - S1 * S1 / a) + ((Qt - Q[use, c]) - S2 * S2 / b), 0.0)
+        s2 = rss / df
+        coef = S2 / b - S1 / a
+        post, _, df0 = _squeeze_var(s2, df)
+        t = coef / (np.sqrt(1.0 / a + 1.0 / b) * np.sqrt(post))
+        dft = min(df + df0, len(use) * df)
+        pv = 2.0 * stats.t.sf(np.abs(t), dft)
+        if cluster_minus_other:
+            coef, t = -coef, -t
+        o = np.argsort(-np.abs(t), kind="stable")
+        parts.append(pd.DataFrame({"logFC": coef[o], "AveExpr": (St / N)[o], "t": t[o], "P.Value": pv[o], "adj.P.Val": p_adjust_fdr(pv)[o],
+                                   "pathway": names[use][o], "cluster": np.repeat(labels[c], len(o))}))
+    return pd.concat(parts, ignore_index=True) if parts else pd.DataFrame({k: [] for k in cols})
+
+
+def runGSVA(data: dict, gmt_file=None, minSize=15, maxSize=np.inf, pathways=None, gene_names=None, convertToEns: bool = False, gene_map=None,
+            nt: int = 2, verbose: bool = True, *, convertHu2Mm: bool = False, cluster_minus_other: bool = False, ctx: Context | None = None) -> dict:
+    """The ``method="GSVA"`` branch of the reference's ``runGSEA`` (R/pathwayAnalisys.R:97-138): GSVA scores of every cell
+    within its cluster (:func:`gsva`, all clusters in one device call) and one limma contrast per cluster on the score matrix
+    (:func:`gsva_de_pathways`).  The clusters are ``data["cluster"]`` in ``unique`` order; pathways and gene names are read as
+    :func:`runGSEA` reads them.  ``nt`` is accepted for signature compatibility.
+
+    ``data["gsva"]`` becomes ``{"pathways", "res", "DEpathways"}``: ``res`` a DataFrame pathways x cells without the rows that
+    are zero everywhere, ``DEpathways`` the limma table ``logFC, AveExpr, t, P.Value, adj.P.Val, pathway, cluster``.  Differences
+    from GSVA and limma (include/gficf_gsva.h): the kernel CDF is exact, there is no ``B`` column, and ``logFC`` keeps the
+    reference's sign, mean(other) - mean(cluster), unless ``cluster_minus_other=True``."""
+    import pandas as pd
+
+    if data.get("gficf") is None:
+        raise ValueError("Please run gficf function first")
+    if data.get("cluster") is None:
+        raise ValueError("Please run clustcell function first")
+    tsmessage("Choosen method is GSVA...", verbose=verbose)
+    if pathways is None:
+        if gmt_file is None:
+            raise ValueError("give gmt_file or pathways=")
+        pathways = gmt_pathways(gmt_file, convertToEns, convertHu2Mm, verbose, gene_map)
+    else:
+        pathways = {str(k): list(v) for k, v in pathways.items() if len(v) > 0}
+    M = data["gficf"]
+    if gene_names is None:
+        gene_names = data.get("gene_names")
+    if gene_names is None and data.get("genes") is not None:
+        gene_names = np.asarray(data["genes"]).astype(str)
+    if gene_names is None or len(gene_names) != M.shape[0]:
+        raise ValueError("gene_names must hold one name per row of data[\"gficf\"]")
+    ids, labels = _first_appearance_ids(data["cluster"], M.shape[1])
+    ptr, rows = _pathway_csr(pathways, gene_names)
+    tsmessage(f"Start executiong GSVA: {len(pathways)} pathways, {len(labels)} clusters", verbose=verbose)
+    r = gsva(M, ids, ptr, rows, minSize, maxSize, False, len(labels), ctx)
+    names = np.asarray(list(pathways))
+    use = (r["es"] != 0).any(axis=1)                         # rowSums(res != 0) > 0
+    tsmessage("Start executiong Limma cluster by cluster", verbose=verbose)
+    data["gsva"] = {"pathways": pathways,
+                    "res": pd.DataFrame(r["es"][use], index=names[use]),
+                    "DEpathways": gsva_de_pathways(r, ids, labels, names, cluster_minus_other)}
     tsmessage("Done!", verbose=verbose)
     return data
 
@@ -2514,6 +2784,39 @@ class HipOps:
         from . import _gsea_lib
 
         check(_gsea_lib.load().gficf_gsea_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def gsva_workspace_bytes(G: int, N: int, C: int, P: int) -> int:
+        """Device scratch of ``gsva_density`` and ``gsva_scores`` (libgficf_gsva.so)."""
+        from . import _gsva_lib
+
+        return int(_gsva_lib.load().gficf_gsva_workspace_bytes(int(G), int(N), int(C), int(P)))
+
+    def gsva_density(self, G, N, C, cluster, seg_ptr, cell, x, max_seg, ws, sd, d0, kept, dnz):
+        """Stages 1-2 of GSVA on device-resident tensors (cluster int32 of N; seg_ptr int64 of G * C + 1, cell int32 and x float64:
+        the entries grouped by (gene, cluster); ws uint8 of ``gsva_workspace_bytes``); sd, d0: (C, G) float64, kept: (C, G) int32,
+        dnz: one float64 per entry.  Enqueues only: ``gsva_sync(ws)`` waits and collects the deferred input errors."""
+        from . import _gsva_lib
+
+        check(_gsva_lib.load().gficf_gsva_density_device(self._bind(), int(G), int(N), int(C), _tptr(cluster), _tptr(seg_ptr), _tptr(cell), _tptr(x),
+                                                         int(x.numel()), int(max_seg), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(sd),
+                                                         _tptr(d0), _tptr(kept), _tptr(dnz)))
+
+    def gsva_scores(self, G, N, C, cluster, colptr, row, src, max_cell_nz, dnz, d0, kept, ptr, members, min_size, max_size, fresh, ws, es, tested,
+                    ssum, ssq):
+        """Stages 3-5 of GSVA and the per-cluster sums on device-resident tensors (colptr int64 of N + 1, row int32, src int64: the
+        entries cell-major); es: (N, P) float64 == column-major P x N; tested int32, ssum, ssq float64: (C, P).  Enqueues only."""
+        from . import _gsva_lib
+
+        check(_gsva_lib.load().gficf_gsva_scores_device(self._bind(), int(G), int(N), int(C), _tptr(cluster), _tptr(colptr), _tptr(row), _tptr(src),
+                                                        int(row.numel()), int(max_cell_nz), _tptr(dnz), _tptr(d0), _tptr(kept), int(ptr.numel()) - 1,
+                                                        _tptr(ptr), _tptr(members), int(members.numel()), int(min_size), int(max_size), int(fresh),
+                                                        _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(es), _tptr(tested), _tptr(ssum), _tptr(ssq)))
+
+    def gsva_sync(self, ws):
+        from . import _gsva_lib
+
+        check(_gsva_lib.load().gficf_gsva_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
