@@ -233,6 +233,13 @@ inline int gficf_bit_width(int64_t n) {
   return b;
 }
 
+// the metrics of the exact searches (gficf_knn_metric): is it one of them, and the one the search itself runs under —
+// gficf_knn_prepare_device centres the rows for correlation, after which it is the cosine search
+inline bool gficf_knn_metric_ok(int metric) {
+  return metric == GFICF_KNN_MANHATTAN || metric == GFICF_KNN_EUCLIDEAN || metric == GFICF_KNN_COSINE || metric == GFICF_KNN_CORRELATION;
+}
+inline int gficf_knn_search_metric(int metric) { return metric == GFICF_KNN_CORRELATION ? GFICF_KNN_COSINE : metric; }
+
 // the lanes of one wave see each other's LDS writes
 #define GFICF_WAVE_SYNC()                                                                                                                 \
   do {                                                                                                                                    \

@@ -4,7 +4,8 @@
 // (include/gficf_transform.h states the algorithm and what is relaxed).
 //
 // Launches (N trained cells, M new cells, k neighbours):
-//   search    k_tr_tiles, k_tr_merge   (transform_search.h) the M x k table over all N training rows
+//   search    k_knn_tiles<.., plain> (knn_tiles.h: the square search's own tile kernel, one text), k_tr_merge (transform_search.h)
+//                              the M x k table over all N training rows
 //   weights   k_tr_smooth      one lane per new cell: rho, the bisection for sigma, the row-local floor, the k memberships; bad ids
 //                              and non-finite distances flagged
 //   init      k_addon_finite, k_tr_init   the trained plane checked; one lane per new cell: the weighted mean of its k heads
@@ -273,10 +274,6 @@ __global__ __launch_bounds__(256) void k_tr_in(const double* __restrict__ in, in
 }
 
 // ------------------------------------------------------------------------------------------------ checks and stage bodies
-bool tr_metric_ok(int metric) {
-  return metric == GFICF_KNN_MANHATTAN || metric == GFICF_KNN_EUCLIDEAN || metric == GFICF_KNN_COSINE || metric == GFICF_KNN_CORRELATION;
-}
-
 int tr_check_table(int64_t N, int64_t M, int k, int64_t ld) {
   if (N < 1 || N > 0x7FFFFFFFll) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "N = %lld outside [1, 2^31)", (long long)N);
   if (M < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "M = %lld: negative", (long long)M);
@@ -291,7 +288,7 @@ int tr_check_search(int64_t N, int64_t M, int d, int k, int metric, int64_t ld) 
   const int rc = tr_check_table(N, M, k, ld);
   if (rc) return rc;
   if (d < 1 || gficf_knn_dpad(d) < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "d = %d outside [1, 128]", d);
-  if (!tr_metric_ok(metric)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "unknown metric %d", metric);
+  if (!gficf_knn_metric_ok(metric)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "unknown metric %d", metric);
   return GFICF_OK;
 }
 
@@ -327,12 +324,12 @@ size_t tr_part_keys(int64_t M, int64_t N, int k) { return (size_t)(M > 0 ? M : 0
 int tr_search(gficf_ctx* ctx, u64* part, const float* d_train, int64_t N, const float* d_query, int64_t M, int d, int k, int metric, int32_t* d_idx,
               float* d_dist, int64_t ld_out) {
   if (M == 0) return GFICF_OK;
-  if (metric == GFICF_KNN_CORRELATION) metric = GFICF_KNN_COSINE;      // the prepared rows are centred: same search
-  TrTileArgs a{};
+  metric = gficf_knn_search_metric(metric);
+  KnnTileArgs a{};                                                // the plain form: no gate, no permutation, no bounds
   a.Q = d_query; a.n_q = M; a.X = d_train; a.N = N; a.d = d; a.dpad = gficf_knn_dpad(d); a.kk = k;
   a.S = tr_split(ctx->num_cus, M, N);
   a.part = part;
-  const int rc = tr_launch_m(ctx, metric, a);
+  const int rc = knn_launch_m<false>(ctx, metric, a);
   if (rc) return rc;
   hipLaunchKernelGGL(k_tr_merge, dim3(tr_grid(M, 4)), dim3(256), 0, ctx->stream, (const u64*)part, M, a.S, k, metric, d_idx, d_dist, ld_out);
   GFICF_HIP_CHECK(hipGetLastError());

@@ -489,8 +489,7 @@ int gficf_umap_host(gficf_ctx* ctx, const double* X, int64_t N, int d, int64_t l
   rc = um_check_layout(N, cap, a, b, gamma, learning_rate, negative_sample_rate, n_epochs, 0, n_epochs);
   if (rc) return rc;
   if (d < 1 || gficf_knn_dpad(d) < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "d = %d outside [1, 128]", d);
-  if (metric != GFICF_KNN_MANHATTAN && metric != GFICF_KNN_EUCLIDEAN && metric != GFICF_KNN_COSINE && metric != GFICF_KNN_CORRELATION)
-    GFICF_FAIL(GFICF_ERR_INVALID_ARG, "unknown metric %d", metric);
+  if (!gficf_knn_metric_ok(metric)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "unknown metric %d", metric);
   if (!X || !init || !embedding) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const bool want_graph = rowptr || col || val || nnz;
   if (want_graph && (!rowptr || !col || !val || !nnz)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "the graph is returned whole: rowptr, col, val and nnz");
