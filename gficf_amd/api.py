@@ -495,16 +495,22 @@ def gficf(M, cell_proportion_max: float = 1, cell_proportion_min: float = 0.05, 
 
     ``normalize=TRUE`` in the reference rescales counts with edgeR TMM/CPM
     (R/gficf.R:43-47) before GF; that is a per-cell scale which cancels in x/colSums(x),
-    so ``gficf`` is unaffected; ``rawCounts`` here always holds the unscaled filtered counts.
+    so ``gficf`` is unaffected; with ``normalize=True`` ``rawCounts`` holds the unscaled filtered counts, with a warning.
+    ``normalize="tmm"`` runs the rescale on the device (:func:`normCounts`, libgficf_tmm.so): ``rawCounts`` holds the TMM
+    counts per million of the kept genes and ``param["normalized"]`` is ``True``; ``gficf`` is the same, bit for bit.
 
     ``icf_type`` / ``norm`` (keyword only, not arguments of the reference's ``gficf()``, which always runs
     "classic" / "l2") select the other branches of its helpers ``getIdfW(type = ...)`` (R/gficf.R:89-91) and
     ``l.norm(norm = ...)`` (R/gficf.R:100).  ``devices`` (or the environment variable GFICF_HIP_DEVICES): a list of GPUs
     to shard the cells over, single process (``gficf_normalize_csc_host_multi_*``); same result.
     """
-    if verbose and normalize:
+    tmm = isinstance(normalize, str)
+    if tmm and normalize != "tmm":
+        raise ValueError('normalize must be True, False or "tmm"')
+    if verbose and normalize and not tmm:
         warnings.warn("normalize=True: the edgeR CPM/TMM rescale (reference R/gficf.R:43-47) is a per-cell scale "
-                      "that cancels in the GF step; rawCounts holds unscaled counts", stacklevel=2)
+                      "that cancels in the GF step; rawCounts holds unscaled counts (normalize=\"tmm\" runs the rescale on the device)",
+                      stacklevel=2)
     # the reference's progress lines (tsmessage: R/gficf.R:58,87,68,99 via R/util.R:30-39; "Normalize counts.." :45 belongs to the
     # edgeR step, which does not run here), same text, on stderr like R's message(); the four steps are ONE device call
     for line in ("Apply GF transformation..", "Compute ICF weigth..", "Applay ICF..", f"Apply {norm}"):
@@ -514,11 +520,14 @@ def gficf(M, cell_proportion_max: float = 1, cell_proportion_min: float = 0.05, 
     data = {"gficf": out}
     if storeRaw:
         data["rawCounts"] = res[5]                        # = M[keep, ] (R/gficf.R:40,22): the result's structure, the counts as values
+        if tmm:                                           # cpm(calcNormFactors(DGEList(counts = M[keep, ]))) (R/gficf.R:46), same structure
+            tsmessage("Normalize counts..", verbose=verbose)
+            data["rawCounts"] = _tmm_host(res[5], want_cpm=True, ctx=ctx)["cpm"]
     data["w"] = w[keep]
     data["genes"] = np.flatnonzero(keep)
     data["nt"] = nt[keep]
     data["param"] = {"cell_proportion_max": cell_proportion_max, "cell_proportion_min": cell_proportion_min,
-                     "normalized": normalize}
+                     "normalized": True if tmm else normalize}
     return data
 
 
@@ -559,6 +568,104 @@ def cluster_signatures(gficf_mat, cluster, ctx: Context | None = None):
                                                     _np_ptr(ids), C, _np_ptr(out)))
     return out.T, uniq[order]
 
+
+# ------------------------------------------------------------------ TMM normalisation (libgficf_tmm.so)
+def _tmm_host(M, ref_col=None, logratioTrim=.3, sumTrim=.05, doWeighting=True, max_lds_n=0, want_cpm=False, ctx: Context | None = None):
+    """``gficf_tmm_host`` on a genes x cells count matrix: the statistics, the reference column, the factors and, with
+    ``want_cpm``, the counts per million as a CSC matrix of ``M``'s structure."""
+    import scipy.sparse as sp
+
+    from . import _tmm_lib
+
+    M, colptr, rowidx, x = _csc_parts(M)
+    G, N = M.shape
+    if G < 1 or N < 1:
+        raise ValueError("the count matrix must hold at least one gene and one cell")
+    for name, v in (("logratioTrim", logratioTrim), ("sumTrim", sumTrim)):
+        if not 0 <= float(v) < .5:
+            raise ValueError(f"{name} must lie in [0, 0.5)")
+    if ref_col is None:
+        ref_col = -1
+    elif not 0 <= int(ref_col) < N:
+        raise ValueError("refColumn must be the (0-based) index of a column of M")
+    lib, sq, f75, raw, f = (np.zeros(N, dtype=np.float64) for _ in range(5))
+    ostat = np.zeros((2, N), dtype=np.float64)
+    n, kept = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+    gp, ref = ctypes.c_int32(0), ctypes.c_int64(-1)
+    out = np.zeros(max(len(x), 1), dtype=np.float64) if want_cpm else None
+    ctx = ctx or default_context()
+    check(_tmm_lib.load().gficf_tmm_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x), int(ref_col),
+                                         float(logratioTrim), float(sumTrim), 1 if doWeighting else 0, int(max_lds_n), None, None, _np_ptr(lib), _np_ptr(sq),
+                                         _np_ptr(f75), _np_ptr(ostat), ctypes.byref(gp), ctypes.byref(ref), _np_ptr(raw), _np_ptr(f), _np_ptr(n), _np_ptr(kept),
+                                         _np_ptr(out)))
+    res = {"norm.factors": f, "lib.size": lib, "refColumn": int(ref.value), "f75": f75, "n": n, "kept": kept, "sq": sq, "ostat": ostat,
+           "Gprime": int(gp.value), "factors.raw": raw}
+    if want_cpm:
+        X = sp.csc_matrix((out[:len(x)], rowidx.copy(), colptr.copy()), shape=(G, N))
+        X.has_sorted_indices = True
+        res["cpm"] = X
+    return res
+
+
+def calcNormFactors(M, refColumn=None, logratioTrim: float = .3, sumTrim: float = .05, doWeighting: bool = True, max_lds_n: int = 0,
+                    ctx: Context | None = None) -> dict:
+    """edgeR's ``calcNormFactors(DGEList(counts = M), method = "TMM")`` on the device, from the sparse matrix (the
+    ``normalize = TRUE`` branch of the reference, R/gficf.R:46), under the contract of include/gficf_tmm.h: the trim ranks on
+    ``obs / ref`` and ``obs * ref``, which tie exactly where the genes are mathematically tied (the tie rule).
+
+    ``M``: genes x cells counts (scipy sparse); ``refColumn``: the 0-based index of the reference column, or ``None`` for
+    edgeR's choice.  Returns ``norm.factors`` (their geometric mean is 1), ``lib.size`` (the column sums), ``refColumn``,
+    ``f75`` (the upper-quartile factor of every column), ``n`` and ``kept`` (the common genes of every cell and the
+    reference, and how many of them survive the trim); also ``sq``, ``ostat``, ``Gprime`` and ``factors.raw`` (the stages).
+    ``max_lds_n`` lowers the LDS capacity beyond which a cell is ranked by the counting kernel (0: the library's)."""
+    return _tmm_host(M, refColumn, logratioTrim, sumTrim, doWeighting, max_lds_n, False, ctx)
+
+
+def cpm(M, lib_size=None, norm_factors=None, ctx: Context | None = None):
+    """edgeR's ``cpm(M, lib.size, norm.factors)``: ``x / (1e-6 * (lib.size * norm.factors))`` on the device, as a CSC
+    matrix of ``M``'s structure (never dense).  ``lib_size=None``: the column sums; ``norm_factors=None``: ones."""
+    import scipy.sparse as sp
+
+    from . import _tmm_lib
+
+    M, colptr, rowidx, x = _csc_parts(M)
+    G, N = M.shape
+    if G < 1 or N < 1:
+        raise ValueError("the count matrix must hold at least one gene and one cell")
+    f = np.ones(N, dtype=np.float64) if norm_factors is None else np.ascontiguousarray(norm_factors, dtype=np.float64)
+    lib = None if lib_size is None else np.ascontiguousarray(lib_size, dtype=np.float64)
+    if f.shape != (N,) or (lib is not None and lib.shape != (N,)):
+        raise ValueError("lib_size and norm_factors must hold one value per cell")
+    out = np.zeros(max(len(x), 1), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_tmm_lib.load().gficf_tmm_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x), -1, .3, .05,
+                                         1, 0, _np_ptr(lib), _np_ptr(f), None, None, None, None, None, None, None, None, None, None, _np_ptr(out)))
+    X = sp.csc_matrix((out[:len(x)], rowidx.copy(), colptr.copy()), shape=(G, N))
+    X.has_sorted_indices = True
+    return X
+
+
+def _norm_counts(M, doc_proportion_max, doc_proportion_min, normalizeCounts, verbose, ctx):
+    """:func:`normCounts`, and the mask of the rows it keeps."""
+    import scipy.sparse as sp
+
+    M = sp.csr_matrix(M)
+    N = M.shape[1]
+    ix = np.diff((M != 0).tocsr().indptr)
+    keep = (ix > N * doc_proportion_min) & (ix <= N * doc_proportion_max)
+    M = sp.csc_matrix(M[keep])
+    if normalizeCounts:
+        tsmessage("Normalize counts..", verbose=verbose)
+        M = _tmm_host(M, want_cpm=True, ctx=ctx)["cpm"]
+    return M, keep
+
+
+def normCounts(M, doc_proportion_max: float = 1, doc_proportion_min: float = .01, normalizeCounts: bool = False, verbose: bool = True,
+               ctx: Context | None = None):
+    """``normCounts(M, doc_proportion_max, doc_proportion_min, normalizeCounts, verbose)`` of the reference (R/gficf.R:38-50):
+    the genes found in more than ``doc_proportion_min`` and at most ``doc_proportion_max`` of the cells and, with
+    ``normalizeCounts``, their TMM counts per million (:func:`calcNormFactors`, :func:`cpm`), sparse."""
+    return _norm_counts(M, doc_proportion_max, doc_proportion_min, normalizeCounts, verbose, ctx)[0]
 
 
 # ------------------------------------------------------------------ marker genes (libgficf_markers.so)
@@ -650,8 +757,9 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     fdr, ``rbind``; the whole table ordered by log2FC, decreasing (both orders stable).  ``data$de.genes`` becomes a
     ``pandas.DataFrame`` with the columns ``ens, log2FC, p.value, fdr, cluster``.
 
-    ``cpms``: the normalised genes x cells matrix (rows as ``data["rawCounts"]``).  The edgeR rescale of the reference's
-    ``normCounts`` is not run here (as in :func:`gficf`): without ``cpms`` the raw counts are tested, with a warning.  Genes
+    ``cpms``: the normalised genes x cells matrix (rows as ``data["rawCounts"]``), or ``"tmm"`` for the reference's own
+    ``normCounts(rawCounts, 2, 0, !normalized)`` (R/deGenes.R:25) on the device (:func:`normCounts`).  Without ``cpms`` the
+    raw counts are tested, with a warning.  Genes
     with no non-zero cell are dropped first (``normCounts(doc_proportion_min = 0)``); the rest set BH's n.  ``hvg=True`` needs
     the locfit fit of ``findVarGenes``, which is not provided: pass ``hvg=False``, or an array of the row indices to keep.
     ``nt`` is accepted for signature compatibility.  ``ens`` holds ``data["genes"]`` of the kept rows (the stand-in for R's
@@ -667,11 +775,19 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     if hvg is True:
         raise NotImplementedError("hvg=True needs findVarGenes (locfit), which is not provided: pass hvg=False, or the row "
                                   "indices of the genes to keep")
-    if cpms is None:
-        warnings.warn("findClusterMarkers: no cpms= given, the raw counts are tested (the edgeR rescale is not run here)", stacklevel=2)
+    kept_rows = None
+    if isinstance(cpms, str):
+        if cpms != "tmm":
+            raise ValueError('cpms must be a matrix, None or "tmm"')
+        cpms, kept_rows = _norm_counts(data["rawCounts"], 2, 0, not (data.get("param") or {}).get("normalized", False), verbose, ctx)
+    elif cpms is None:
+        warnings.warn("findClusterMarkers: no cpms= given, the raw counts are tested (the edgeR rescale is not run here; cpms=\"tmm\" "
+                      "runs it on the device)", stacklevel=2)
         cpms = data["rawCounts"]
     M = sp.csr_matrix(cpms)
     names = np.asarray(data["genes"]) if data.get("genes") is not None and len(data["genes"]) == M.shape[0] else np.arange(M.shape[0])
+    if kept_rows is not None and not kept_rows.all():        # normCounts dropped rows: the names follow
+        names = np.asarray(data["genes"])[kept_rows] if data.get("genes") is not None and len(data["genes"]) == len(kept_rows) else np.flatnonzero(kept_rows)
     rows = np.arange(M.shape[0]) if hvg is False or hvg is None else np.asarray(hvg, dtype=np.int64)
     M = M[rows]
     keep = np.diff((M != 0).tocsr().indptr) > 0             # normCounts(doc_proportion_min = 0): rowSums(M != 0) > 0
@@ -2817,6 +2933,48 @@ class HipOps:
         from . import _gsva_lib
 
         check(_gsva_lib.load().gficf_gsva_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def tmm_workspace_bytes(G: int, N: int, big_cells: int = 0, big_entries: int = 0) -> int:
+        """Device scratch of ``tmm_stats``, ``tmm_factors`` and ``tmm_cpm`` (libgficf_tmm.so).  ``big_cells``, ``big_entries``: the
+        cells with more stored entries than the LDS capacity (``_tmm_lib.LDS_N``, or ``max_lds_n``) and their entries together."""
+        from . import _tmm_lib
+
+        return int(_tmm_lib.load().gficf_tmm_workspace_bytes(int(G), int(N), int(big_cells), int(big_entries)))
+
+    def tmm_stats(self, G, N, colptr, rowidx, x, max_cell_nz, ws, lib, sq, f75, ostat, gprime, max_lds_n: int = 0):
+        """Stage 1 of TMM on device-resident tensors (colptr int32 or int64 of N + 1, rowidx int32, x float64; ws uint8 of
+        ``tmm_workspace_bytes``): lib, sq, f75 float64 of N, ostat float64 (2, N), gprime int32 of 1.  Enqueues only:
+        ``tmm_sync(ws)`` waits and collects the deferred input errors."""
+        from . import _tmm_lib
+
+        check(_tmm_lib.load().gficf_tmm_stats_device(self._bind(), int(G), int(N), _tptr(colptr), 1 if colptr.element_size() == 8 else 0, _tptr(rowidx),
+                                                     _tptr(x), int(x.numel()), int(max_cell_nz), int(max_lds_n), _tptr(ws),
+                                                     int(ws.numel() * ws.element_size()), _tptr(lib), _tptr(sq), _tptr(f75), _tptr(ostat), _tptr(gprime)))
+
+    def tmm_factors(self, G, N, colptr, rowidx, x, max_cell_nz, ref_col, lib, ws, factor, n, kept, logratioTrim=.3, sumTrim=.05, doWeighting=True,
+                    max_lds_n: int = 0, big_cells: int = 0, big_entries: int = 0, fresh: bool = True):
+        """Stage 2 of TMM on device-resident tensors: the factor (float64, not yet normalised), n and kept (int32) of every
+        cell against column ``ref_col``, from the library sizes ``lib``.  Enqueues only."""
+        from . import _tmm_lib
+
+        check(_tmm_lib.load().gficf_tmm_factors_device(self._bind(), int(G), int(N), _tptr(colptr), 1 if colptr.element_size() == 8 else 0, _tptr(rowidx),
+                                                       _tptr(x), int(x.numel()), int(max_cell_nz), int(ref_col), _tptr(lib), float(logratioTrim),
+                                                       float(sumTrim), 1 if doWeighting else 0, int(max_lds_n), int(big_cells), int(big_entries),
+                                                       1 if fresh else 0, _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(factor), _tptr(n),
+                                                       _tptr(kept)))
+
+    def tmm_cpm(self, N, colptr, x, lib, factor, ws, out):
+        """Stage 3: ``out = x / (1e-6 * (lib * factor))`` per stored entry, on device-resident tensors.  Enqueues only."""
+        from . import _tmm_lib
+
+        check(_tmm_lib.load().gficf_tmm_cpm_device(self._bind(), int(N), _tptr(colptr), 1 if colptr.element_size() == 8 else 0, _tptr(x), int(x.numel()),
+                                                   _tptr(lib), _tptr(factor), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(out)))
+
+    def tmm_sync(self, ws):
+        from . import _tmm_lib
+
+        check(_tmm_lib.load().gficf_tmm_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
