@@ -750,6 +750,194 @@ def p_adjust_fdr(p) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------ highly variable genes (libgficf_hvg.so)
+def _hvg_outputs(G: int, stages: bool) -> dict:
+    from . import _hvg_lib
+
+    o = {k: np.full(G, np.nan, dtype=np.float64) for k in ("lx", "ly", "fit", "weights", "cvDist", "P")}
+    o["valid"] = np.zeros(G, dtype=np.int32)
+    o["scalars"] = np.full(len(_hvg_lib.SCALARS), np.nan, dtype=np.float64)
+    if stages:
+        o["g5"], o["ySeq"] = np.zeros(_hvg_lib.GRID5_MAX, dtype=np.float64), np.zeros(_hvg_lib.GRID5_MAX, dtype=np.float64)
+        o["gap"] = np.zeros(_hvg_lib.GRID5_MAX, dtype=np.int32)
+    return o
+
+
+def _hvg_result(o: dict, mean, cv, stages: bool) -> dict:
+    """The outputs of the host entries as the dictionary of :func:`var_genes_from_moments`."""
+    from . import _hvg_lib
+
+    sc = dict(zip(_hvg_lib.SCALARS, o["scalars"]))
+    valid = o["valid"] != 0
+    fdr = np.full(len(valid), np.nan, dtype=np.float64)
+    fdr[valid] = p_adjust_fdr(o["P"][valid])
+    r = {"mean": mean, "cv": cv, "P": o["P"], "FDR": fdr}
+    if stages:
+        n5 = int(sc["len5"])
+        r.update({k: o[k] for k in ("lx", "ly", "fit", "weights", "cvDist")})
+        r.update({"valid": valid, "s": np.array([sc["s0"], sc["s1"], sc["s2"]]), "g5": o["g5"][:n5].copy(), "gap": o["gap"][:n5].copy(),
+                  "ySeq": o["ySeq"][:n5].copy()})
+        r.update({k: int(sc[k]) for k in ("n", "k", "cdx0", "j0", "nls_iter")})
+        r.update({k: float(sc[k]) for k in ("b", "a", "bw", "distMid", "mu", "sigma")})
+    return r
+
+
+def _hvg_enough(n_valid: int) -> None:
+    if int(np.floor(0.2 * n_valid)) < 4:
+        raise ValueError(f"{n_valid} genes with a finite log10 mean and log10 cv: the local regression needs at least 20")
+
+
+def gene_moments(M, ctx: Context | None = None) -> dict:
+    """Per-gene moments of the genes x cells matrix ``M`` (scipy sparse, at least 2 cells) in one pass over its stored entries
+    (step 1 of include/gficf_hvg.h): ``mean``, ``sd`` and ``var`` (the n - 1 denominator, two passes as R's ``sd``), ``nobs``
+    (the stored non-zeros), and ``lx = log10(mean)``, ``ly = log10(sd / mean)``, ``valid`` (both finite)."""
+    from . import _hvg_lib
+
+    M, colptr, rowidx, x = _csc_parts(M)
+    G, N = M.shape
+    if G < 1 or N < 2:
+        raise ValueError("the matrix must hold at least one gene and two cells")
+    mean, sd, var, lx, ly = (np.zeros(G, dtype=np.float64) for _ in range(5))
+    nobs, valid = np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int32)
+    ctx = ctx or default_context()
+    check(_hvg_lib.load().gficf_hvg_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x), 1,
+                                         _np_ptr(mean), _np_ptr(sd), _np_ptr(var), _np_ptr(nobs), _np_ptr(lx), _np_ptr(ly), _np_ptr(valid), None, None,
+                                         None, None, None, None, None, None))
+    return {"mean": mean, "sd": sd, "var": var, "nobs": nobs, "lx": lx, "ly": ly, "valid": valid != 0}
+
+
+def var_genes_from_moments(mean, cv, ctx: Context | None = None) -> dict:
+    """Steps 2 - 7 of :func:`findVarGenes` from the genes' ``mean`` and ``cv`` (include/gficf_hvg.h): the robust local
+    regression of log10 cv on log10 mean, the trusted range, the curve ``0.5 * log10(b / x + a)``, the signed distances, their
+    mode and the p-values.  Returns every stage: ``lx, ly, valid, fit, weights, s`` (3), ``g5, gap, ySeq, cdx0, j0, b, a,
+    nls_iter, cvDist, bw, distMid, mu, sigma, P, FDR`` (per-gene arrays hold NaN at the invalid genes), and ``n``, ``k``."""
+    from . import _hvg_lib
+
+    mean, cv = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(cv, dtype=np.float64)
+    if mean.ndim != 1 or mean.shape != cv.shape or len(mean) < 1:
+        raise ValueError("mean and cv must be vectors of one length")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        _hvg_enough(int((np.isfinite(np.log10(mean)) & np.isfinite(np.log10(cv))).sum()))
+    o = _hvg_outputs(len(mean), True)
+    ctx = ctx or default_context()
+    check(_hvg_lib.load().gficf_hvg_trend_host(ctx.handle, len(mean), _np_ptr(mean), _np_ptr(cv), _np_ptr(o["lx"]), _np_ptr(o["ly"]), _np_ptr(o["valid"]),
+                                               _np_ptr(o["fit"]), _np_ptr(o["weights"]), _np_ptr(o["cvDist"]), _np_ptr(o["P"]), _np_ptr(o["scalars"]),
+                                               _np_ptr(o["g5"]), _np_ptr(o["gap"]), _np_ptr(o["ySeq"])))
+    return _hvg_result(o, mean, cv, True)
+
+
+def findVarGenes(cpms, fitMethod: str = "locfit", verbose: bool = True, genes=None, ret_stages: bool = False, ctx: Context | None = None):
+    """``findVarGenes(data, fitMethod, verbose)`` of the reference (R/deGenes.R:72-164; scVEGs, Chen et al. 2016) on the
+    device, from the sparse matrix, under the contract of include/gficf_hvg.h.  ``cpms``: the normalised genes x cells
+    counts.  Returns a ``pandas.DataFrame`` with the columns ``gene, mean, cv, P, FDR``, one row per row of ``cpms`` in its
+    order (``gene``: ``genes``, or the row index); a gene without a finite log10 mean and log10 cv has NaN in P and FDR.
+    ``ret_stages=True``: a dictionary with those columns and every stage of :func:`var_genes_from_moments`, and ``sd``,
+    ``var``, ``nobs``.  Only ``fitMethod="locfit"`` (the one ``findClusterMarkers`` uses) is provided."""
+    from . import _hvg_lib
+
+    if fitMethod != "locfit":
+        raise NotImplementedError(f'fitMethod="{fitMethod}" is not provided: only "locfit", the fit findClusterMarkers() asks for')
+    M, colptr, rowidx, x = _csc_parts(cpms)
+    G, N = M.shape
+    if N < 2:
+        raise ValueError("the standard deviation of a gene needs at least 2 cells")
+    if genes is not None and len(genes) != G:
+        raise ValueError("genes must hold one name per row of cpms")
+    _hvg_enough(G)
+    o = _hvg_outputs(G, ret_stages)
+    mean, sd, var = (np.zeros(G, dtype=np.float64) for _ in range(3))
+    nobs = np.zeros(G, dtype=np.int32)
+    ctx = ctx or default_context()
+    check(_hvg_lib.load().gficf_hvg_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x), 0,
+                                         _np_ptr(mean), _np_ptr(sd), _np_ptr(var), _np_ptr(nobs), _np_ptr(o["lx"]), _np_ptr(o["ly"]), _np_ptr(o["valid"]),
+                                         _np_ptr(o["fit"]), _np_ptr(o["weights"]), _np_ptr(o["cvDist"]), _np_ptr(o["P"]), _np_ptr(o["scalars"]),
+                                         _np_ptr(o.get("g5")), _np_ptr(o.get("gap")), _np_ptr(o.get("ySeq"))))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = _hvg_result(o, mean, sd / mean, ret_stages)
+    r["gene"] = np.arange(G) if genes is None else np.asarray(genes)
+    if ret_stages:
+        r.update({"sd": sd, "var": var, "nobs": nobs})
+        return r
+    import pandas as pd
+
+    return pd.DataFrame({k: r[k] for k in ("gene", "mean", "cv", "P", "FDR")})
+
+
+def _hvg_vectors(*arrays):
+    out = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    if any(a.ndim != 1 or a.shape != out[0].shape for a in out) or len(out[0]) < 1:
+        raise ValueError("the arguments must be vectors of one length")
+    if not all(np.isfinite(a).all() for a in out):
+        raise ValueError("the arguments must be finite")
+    return out
+
+
+def local_regression(x, y, at=None, nn: float = 0.2, weights=None, robust_iter: int = 0, ret_h: bool = False, device: int = 0):
+    """The local regression of :func:`findVarGenes` on its own (step 2 of include/gficf_hvg.h; locfit's ``lp(x, nn)`` at
+    ``deg = 2`` with the tricube kernel, every value a direct fit): ``y`` on ``x`` over the ``floor(nn * n)`` nearest points,
+    evaluated at ``at`` (``None``: at ``x``).  ``weights``: prior weights of the points; ``robust_iter``: rounds of
+    Cleveland's bisquare reweighting before the returned fit (``locfit.robust`` runs 3).  ``ret_h=True``: also the bandwidth
+    at every evaluation point."""
+    x, y = _hvg_vectors(x, y)
+    n = len(x)
+    k = int(np.floor(nn * n))
+    if not 1 <= k <= n:
+        raise ValueError("nn must leave between 1 and all of the points in a window")
+    wv = None
+    if weights is not None:
+        (wv,) = _hvg_vectors(weights)
+        if wv.shape != x.shape or (wv < 0).any():
+            raise ValueError("weights must hold one non-negative value per point")
+    if at is not None:
+        (at,) = _hvg_vectors(at)
+    ops = _umap_hip(device)
+    tc = ops.torch
+    dev = tc.device("cuda", device)
+    t = lambda v: tc.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
+    d_x = t(x)
+    ws = tc.empty(ops.hvg_workspace_bytes(n), dtype=tc.uint8, device=dev)
+    perm, count = tc.empty(n, dtype=tc.int32, device=dev), tc.empty(1, dtype=tc.int32, device=dev)
+    ops.hvg_order(d_x, None, ws, perm, count)
+    perm = perm.long()
+    xs, ys = d_x[perm].contiguous(), t(y)[perm].contiguous()
+    w = None if wv is None else t(wv)[perm].contiguous()
+    if robust_iter > 0:
+        w_out, f_n, s = tc.empty(n, dtype=tc.float64, device=dev), tc.empty(n, dtype=tc.float64, device=dev), tc.empty(int(robust_iter), dtype=tc.float64, device=dev)
+        ops.hvg_robust(xs, ys, k, int(robust_iter), ws, w_out, f_n, s, w_in=w)
+        w = w_out
+    d_at = d_x if at is None else t(at)
+    fit, h = tc.empty(d_at.numel(), dtype=tc.float64, device=dev), tc.empty(d_at.numel(), dtype=tc.float64, device=dev)
+    ops.hvg_locfit(xs, ys, w, k, d_at, ws, fit, h)
+    ops.hvg_sync(ws)
+    return (fit.cpu().numpy(), h.cpu().numpy()) if ret_h else fit.cpu().numpy()
+
+
+def curve_distance(lx, ly, b: float, a: float, ret_index: bool = False, device: int = 0):
+    """Step 5 of :func:`findVarGenes` on its own: the signed distance ``cvDist`` of every gene ``(lx, ly)`` to the curve
+    ``0.5 * log10(b / 10^g + a)`` on the grid ``g = seq(min lx, max lx, 0.001)``.  ``ret_index=True``: also the index of the
+    nearest grid point."""
+    lx, ly = _hvg_vectors(lx, ly)
+    x0 = float(lx.min())
+    glen = int(np.floor((float(lx.max()) - x0) / 0.001 + 1e-10)) + 1
+    ops = _umap_hip(device)
+    tc = ops.torch
+    dev = tc.device("cuda", device)
+    ws = tc.empty(ops.hvg_workspace_bytes(len(lx), grid_pts=glen), dtype=tc.uint8, device=dev)
+    out, idx = tc.empty(len(lx), dtype=tc.float64, device=dev), tc.empty(len(lx), dtype=tc.int32, device=dev)
+    ops.hvg_curve_distance(tc.from_numpy(lx).to(dev), tc.from_numpy(ly).to(dev), b, a, x0, glen, ws, out, idx)
+    ops.hvg_sync(ws)
+    return (out.cpu().numpy(), idx.cpu().numpy()) if ret_index else out.cpu().numpy()
+
+
+def hvg_rows(fdr) -> np.ndarray:
+    """The rows ``findClusterMarkers(hvg = TRUE)`` keeps, in its order (R/deGenes.R:31-35): ordered stably by FDR (NaN last),
+    those with FDR < .1 or, if they are at most 1000, the first ``min(1000, G)``."""
+    fdr = np.asarray(fdr, dtype=np.float64)
+    o = np.argsort(fdr, kind="stable")
+    sig = int((fdr[o] < .1).sum())
+    return o[:sig] if sig > 1000 else o[:min(1000, len(o))]
+
+
 def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, cpms=None, ctx: Context | None = None) -> dict:
     """``findClusterMarkers(data, nt, hvg, verbose)`` of the reference (R/deGenes.R:15-60): marker genes of every cluster, the
     Mann-Whitney U test of each cluster against the rest on the device (``cluster_markers``), then the reference's R
@@ -760,8 +948,11 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     ``cpms``: the normalised genes x cells matrix (rows as ``data["rawCounts"]``), or ``"tmm"`` for the reference's own
     ``normCounts(rawCounts, 2, 0, !normalized)`` (R/deGenes.R:25) on the device (:func:`normCounts`).  Without ``cpms`` the
     raw counts are tested, with a warning.  Genes
-    with no non-zero cell are dropped first (``normCounts(doc_proportion_min = 0)``); the rest set BH's n.  ``hvg=True`` needs
-    the locfit fit of ``findVarGenes``, which is not provided: pass ``hvg=False``, or an array of the row indices to keep.
+    with no non-zero cell are dropped first (``normCounts(doc_proportion_min = 0)``); the rest set BH's n.  ``hvg="locfit"``
+    runs the reference's selection (R/deGenes.R:27-37) with :func:`findVarGenes` on the device: the genes ordered by FDR, those
+    below 10 % or, if they are at most 1000, the first 1000, tested in that order.  ``hvg=True`` stands for the reference's
+    own locfit fit (at kd-tree vertices, interpolated), which is not provided: pass ``hvg="locfit"`` (every value a direct
+    fit), ``hvg=False``, or an array of the row indices to keep.
     ``nt`` is accepted for signature compatibility.  ``ens`` holds ``data["genes"]`` of the kept rows (the stand-in for R's
     rownames) or, without it, the row indices.
     """
@@ -773,8 +964,11 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     if data.get("rawCounts") is None:
         raise ValueError("No raw/normalized counts stored. You should have run gficf normalization with storeRaw = T")
     if hvg is True:
-        raise NotImplementedError("hvg=True needs findVarGenes (locfit), which is not provided: pass hvg=False, or the row "
-                                  "indices of the genes to keep")
+        raise NotImplementedError("hvg=True is the reference's locfit fit at kd-tree vertices, which is not provided: pass "
+                                  "hvg=\"locfit\" for findVarGenes with every value a direct fit (include/gficf_hvg.h), hvg=False, or the "
+                                  "row indices of the genes to keep")
+    if isinstance(hvg, str) and hvg != "locfit":
+        raise ValueError('hvg must be "locfit", False or the row indices of the genes to keep')
     kept_rows = None
     if isinstance(cpms, str):
         if cpms != "tmm":
@@ -788,7 +982,14 @@ def findClusterMarkers(data: dict, nt: int = 2, hvg=True, verbose: bool = True, 
     names = np.asarray(data["genes"]) if data.get("genes") is not None and len(data["genes"]) == M.shape[0] else np.arange(M.shape[0])
     if kept_rows is not None and not kept_rows.all():        # normCounts dropped rows: the names follow
         names = np.asarray(data["genes"])[kept_rows] if data.get("genes") is not None and len(data["genes"]) == len(kept_rows) else np.flatnonzero(kept_rows)
-    rows = np.arange(M.shape[0]) if hvg is False or hvg is None else np.asarray(hvg, dtype=np.int64)
+    if isinstance(hvg, str):                                 # R/deGenes.R:27-37 on the rows normCounts(doc_proportion_min = 0) leaves
+        tsmessage("... Detecting HVGs", verbose=verbose)
+        left = np.flatnonzero(np.diff((M != 0).tocsr().indptr) > 0)
+        fdr = findVarGenes(M[left], verbose=verbose, ctx=ctx)["FDR"].to_numpy()
+        tsmessage(f"... Detected {int((fdr < .1).sum())} significant HVGs with an FDR < 10%", verbose=verbose)
+        rows = left[hvg_rows(fdr)]
+    else:
+        rows = np.arange(M.shape[0]) if hvg is False or hvg is None else np.asarray(hvg, dtype=np.int64)
     M = M[rows]
     keep = np.diff((M != 0).tocsr().indptr) > 0             # normCounts(doc_proportion_min = 0): rowSums(M != 0) > 0
     rows, M = rows[keep], sp.csc_matrix(M[keep])
@@ -2975,6 +3176,76 @@ class HipOps:
         from . import _tmm_lib
 
         check(_tmm_lib.load().gficf_tmm_sync(self._bind(), _tptr(ws)))
+
+    # -- highly variable genes (libgficf_hvg.so); every stage enqueues only: ``hvg_sync(ws)`` waits and collects the deferred errors
+    @staticmethod
+    def hvg_workspace_bytes(G: int, N: int = 0, nnz: int = 0, grid_pts: int = 0) -> int:
+        """Device scratch of the ``hvg_*`` stages for lists of up to ``G`` values, the gene-major view of a G x N matrix of
+        ``nnz`` entries (``hvg_moments`` only) and grids of up to ``grid_pts`` points (``hvg_curve_distance`` only)."""
+        from . import _hvg_lib
+
+        return int(_hvg_lib.load().gficf_hvg_workspace_bytes(int(G), int(N), int(nnz), int(grid_pts)))
+
+    def hvg_moments(self, G, N, colptr, rowidx, x, ws, mean, sd, var, nobs, lx, ly, valid):
+        """Step 1 on device-resident tensors (colptr int64 of N + 1, rowidx int32, x float64): mean, sd, var, lx, ly float64
+        of G, nobs and valid int32 of G."""
+        from . import _hvg_lib
+
+        if colptr.element_size() != 8:
+            raise ValueError("colptr must be int64")
+        check(_hvg_lib.load().gficf_hvg_moments_device(self._bind(), int(G), int(N), _tptr(colptr), _tptr(rowidx), _tptr(x), int(x.numel()), _tptr(ws),
+                                                       int(ws.numel() * ws.element_size()), _tptr(mean), _tptr(sd), _tptr(var), _tptr(nobs), _tptr(lx),
+                                                       _tptr(ly), _tptr(valid)))
+
+    def hvg_order(self, key, valid, ws, perm, count):
+        """The stable ascending order of ``key`` (float64) into ``perm`` (int32), the positions with ``valid == 0`` last
+        (``valid`` None: all count); ``count`` (int32 of 1): how many count."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_order_device(self._bind(), int(key.numel()), _tptr(key), _tptr(valid), _tptr(ws),
+                                                     int(ws.numel() * ws.element_size()), _tptr(perm), _tptr(count)))
+
+    def hvg_locfit(self, xs, ys, w, k, at, ws, fit, h=None):
+        """The local quadratic fit at the points ``at`` from the ascending ``xs``, ``ys`` and weights ``w`` (None: ones) over the
+        ``k`` nearest; ``fit`` and ``h`` (optional): float64 of ``len(at)``."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_locfit_device(self._bind(), int(xs.numel()), _tptr(xs), _tptr(ys), _tptr(w), int(k), int(at.numel()), _tptr(at),
+                                                      _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(fit), _tptr(h)))
+
+    def hvg_robust(self, xs, ys, k, iters, ws, w, fit, s, w_in=None):
+        """Cleveland's loop: ``iters + 1`` fits at the data, the weights from 1 (or ``w_in``); ``w``, ``fit``: float64 of n, ``s``: of iters."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_robust_device(self._bind(), int(xs.numel()), _tptr(xs), _tptr(ys), _tptr(w_in), int(k), int(iters), _tptr(ws),
+                                                      int(ws.numel() * ws.element_size()), _tptr(w), _tptr(fit), _tptr(s)))
+
+    def hvg_gap(self, xs, x0, step, half, ws, grid, gap):
+        """``grid[i] = x0 + i * step`` and the points of the ascending ``xs`` in ``[grid[i] - half, grid[i] + half)`` (int32)."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_gap_device(self._bind(), int(xs.numel()), _tptr(xs), float(x0), float(step), float(half), int(grid.numel()),
+                                                   _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(grid), _tptr(gap)))
+
+    def hvg_curve_distance(self, lx, ly, b, a, x0, grid_len, ws, cvdist, index=None):
+        """Step 5: the signed distance of every (lx, ly) to the curve (b, a) on the grid ``x0 + i * 0.001``, ``i < grid_len``."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_curve_distance_device(self._bind(), int(lx.numel()), _tptr(lx), _tptr(ly), float(b), float(a), float(x0),
+                                                              int(grid_len), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(cvdist), _tptr(index)))
+
+    def hvg_kde(self, v, ws, stats, dens, argmax):
+        """Step 6: ``stats`` float64 of 8 (bw, distMid, grid lo, grid hi, sd, the quartiles, mean), ``dens`` float64 of 512,
+        ``argmax`` int32 of 1."""
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_kde_device(self._bind(), int(v.numel()), _tptr(v), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(stats),
+                                                   _tptr(dens), _tptr(argmax)))
+
+    def hvg_sync(self, ws):
+        from . import _hvg_lib
+
+        check(_hvg_lib.load().gficf_hvg_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
