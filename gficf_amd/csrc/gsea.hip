@@ -6,12 +6,14 @@
 // of the genes, and its permutation null only on (G, set size).  One null table (nsim values per distinct size) serves every
 // pathway of that size in every cluster.  A set of positions is a bit mask of G bits in LDS and its running sum a popcount scan,
 // so one walker scores the observed sets and the random ones, without a sort per set.  Launches, all on the context's stream:
-//   k_gs_keys        order-preserving descending 64-bit key of every statistic (-0.0 -> +0.0; NaN / Inf flagged)
-//   3 radix sorts    stable LSD by the key's low 32 bits, its high 32 bits, then the cluster: (cluster, statistic desc, row) order
+//   (addon_sort.h)   k_sort_keys: order-preserving descending 64-bit key of every statistic (-0.0 -> +0.0; NaN / Inf flagged);
+//                    3 radix sorts, stable LSD by the key's low 32 bits, its high 32 bits, then the cluster (k_sort_next
+//                    between them): (cluster, statistic desc, row) order
 //   k_gs_rank        r_c(g), the position of gene g in cluster c's order
 //   k_gs_es<false>   one workgroup per (pathway, cluster): the observed ES
 //   per batch of B permutations:
-//     k_gs_perm_keys (key_j(g), j, g); 2 radix sorts: by the 32-bit key, then stably by the batch-local j -> the rows pi_j
+//     k_gs_perm_keys (key_j(g), j, g); 2 radix sorts: by the 32-bit key, then (k_sort_next<1>) stably by the batch-local j
+//                    -> the rows pi_j
 //     k_gs_es<true>  one workgroup per (size, permutation): null[d][j], the ES of the first m entries of pi_j
 //   k_gs_null_sums   per size: the counts and fixed-order sums of its null row
 //   k_gs_stats       one wave per (pathway, cluster): the counts against its size's null row, NES and pval
@@ -19,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_sort.h"
 #include "addon_status.h"
 #include "common.h"
 #include "gficf_gsea.h"
@@ -43,34 +46,6 @@ struct GsNull {                                       // per distinct size, over
 __host__ __device__ inline uint32_t gs_mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
   return x;
-}
-
-// ascending order of the key = descending order of the statistic; -0.0 ties with +0.0
-__device__ inline u64 gs_key(double v) {
-  if (v == 0.0) v = 0.0;
-  const u64 b = (u64)__double_as_longlong(v);
-  return ~((b >> 63) ? ~b : (b | (1ull << 63)));
-}
-
-__global__ __launch_bounds__(256) void k_gs_keys(int64_t n, const double* __restrict__ stats, u64* __restrict__ key, u64* __restrict__ kv,
-                                                 uint32_t* __restrict__ status) {
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
-    const double v = stats[p];
-    if (!isfinite(v)) atomicOr(status, GS_ST_VALUE);
-    const u64 k = gs_key(v);
-    key[p] = k;
-    kv[p] = (k << 32) | (u64)p;                            // first pass: the key's low 32 bits
-  }
-}
-
-// next pass: (PART 0: the key's high 32 bits, PART 1: the group value / G) << 32 | value, in the order of the previous pass
-template <int PART>
-__global__ __launch_bounds__(256) void k_gs_kv(int64_t n, uint32_t G, const uint32_t* __restrict__ val, const u64* __restrict__ key, u64* __restrict__ kv) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const uint32_t p = val[i];
-    const u64 hi = PART == 0 ? (key[p] >> 32) : (u64)(p / G);
-    kv[i] = (hi << 32) | (u64)p;
-  }
 }
 
 // sorted position i holds statistic val[i] = c * G + g; every cluster has G of them, so cluster c fills [c * G, (c + 1) * G)
@@ -243,8 +218,8 @@ __global__ __launch_bounds__(256) void k_gs_stats(int64_t P, int64_t total, int3
       nge += x >= e ? 1 : 0;
       nle += x <= e ? 1 : 0;
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { nge += __shfl_xor(nge, s); nle += __shfl_xor(nle, s); }
+    nge = gficf_wave_sum(nge);
+    nle = gficf_wave_sum(nle);
     if (lane == 0) {
       const GsNull s = nsum[d];
       nes[q] = e / (e > 0.0 ? s.ge_zero_mean : fabs(s.le_zero_mean));
@@ -256,9 +231,7 @@ __global__ __launch_bounds__(256) void k_gs_stats(int64_t P, int64_t total, int3
 // ------------------------------------------------------- workspace
 struct GsWs {
   uint32_t* status;
-  u64 *key, *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval;
+  gficf_sort_bufs sort;
   int32_t* rank;
   GsNull* nsum;
   double* null;
@@ -277,23 +250,12 @@ static size_t gs_carve(char* base, int64_t G, int64_t C, int64_t D, int64_t nsim
   cv.base = base;
   const int64_t gc = G * C, bg = gs_batch(G, nsim) * G, nmax = std::max<int64_t>(std::max(gc, bg), 1);
   w.status = cv.take<uint32_t>(1);
-  w.key = cv.take<u64>((size_t)std::max<int64_t>(gc, 1));
-  w.kv0 = cv.take<u64>((size_t)nmax + 1);
-  w.kv1 = cv.take<u64>((size_t)nmax + 1);
-  const int64_t h32 = gficf_radix_sort_hist_len(nmax, 32), hc = gficf_radix_sort_hist_len(nmax, gficf_bit_width(C - 1)),
-                hb = gficf_radix_sort_hist_len(nmax, gficf_bit_width(GS_BATCH_MAX - 1));            // the widest digit of any pass made
-  w.hist = cv.take<int64_t>((size_t)std::max(h32, std::max(hc, hb)));
-  w.okey = cv.take<uint32_t>((size_t)nmax);
-  w.oval = cv.take<uint32_t>((size_t)nmax);
+  // the statistics have 64-bit keys, a batch of permutations has the more elements; the cluster and the batch-local j are groups
+  w.sort.take(cv, (size_t)std::max<int64_t>(gc, 1), (size_t)nmax, {gficf_bit_width(C - 1), gficf_bit_width(GS_BATCH_MAX - 1)});
   w.rank = cv.take<int32_t>((size_t)std::max<int64_t>(gc, 1));
   w.nsum = cv.take<GsNull>((size_t)std::max<int64_t>(D, 1));
   w.null = cv.take<double>((size_t)std::max<int64_t>(D * nsim, 1));
   return cv.total();
-}
-
-static unsigned gs_grid(int64_t n) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, 256);
-  return (unsigned)(b < 16384 ? b : 16384);
 }
 
 static int gs_check_sizes(int64_t G, int64_t C, int64_t P, int64_t n_members, int64_t D, int64_t nsim) {
@@ -306,17 +268,18 @@ static int gs_check_sizes(int64_t G, int64_t C, int64_t P, int64_t n_members, in
   return GFICF_OK;
 }
 
-// the rows pi_(j0) ... pi_(j0 + bc - 1) into w.oval (row jb at [jb * G, (jb + 1) * G), its entries offset by jb * G)
-static int gs_permutations(gficf_ctx* ctx, u64* kv0, u64* kv1, int64_t* hist, uint32_t* okey, uint32_t* oval, int64_t G, uint32_t seed, int64_t j0, int64_t bc) {
+// the rows pi_(j0) ... pi_(j0 + bc - 1) into s.oval (row jb at [jb * G, (jb + 1) * G), its entries offset by jb * G)
+static int gs_permutations(gficf_ctx* ctx, const gficf_sort_bufs& s, int64_t G, uint32_t seed, int64_t j0, int64_t bc) {
   hipStream_t st = ctx->stream;
   const int64_t n = bc * G;
-  hipLaunchKernelGGL(k_gs_perm_keys, dim3(gs_grid(n)), dim3(256), 0, st, n, (uint32_t)G, gs_mix32(seed), (uint32_t)j0, kv0);
+  hipLaunchKernelGGL(k_gs_perm_keys, dim3(gficf_grid_1d(n)), dim3(256), 0, st, n, (uint32_t)G, gs_mix32(seed), (uint32_t)j0, s.kv0);
   GFICF_HIP_CHECK(hipGetLastError());
-  int rc = gficf_radix_sort_kv(ctx, kv0, kv1, hist, n, 32, okey, oval);                             // the 32-bit key
+  int rc = gficf_radix_sort_kv(ctx, s.kv0, s.kv1, s.hist, n, 32, s.okey, s.oval);                   // the 32-bit key
   if (rc || bc == 1) return rc;
-  hipLaunchKernelGGL(k_gs_kv<1>, dim3(gs_grid(n)), dim3(256), 0, st, n, (uint32_t)G, (const uint32_t*)oval, (const u64*)nullptr, kv0);
+  hipLaunchKernelGGL(k_sort_next<1>, dim3(gficf_grid_1d(n)), dim3(256), 0, st, n, (const uint32_t*)s.oval, (const u64*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t)G, s.kv0);
   GFICF_HIP_CHECK(hipGetLastError());
-  return gficf_radix_sort_kv(ctx, kv0, kv1, hist, n, gficf_bit_width(bc - 1), okey, oval);          // the batch-local j, stably
+  return gficf_radix_sort_kv(ctx, s.kv0, s.kv1, s.hist, n, gficf_bit_width(bc - 1), s.okey, s.oval);   // the batch-local j, stably
 }
 
 }  // namespace
@@ -342,26 +305,15 @@ int gficf_gsea_device(gficf_ctx* ctx, int64_t G, int32_t C, const double* d_stat
   if (!d_stats || !d_ptr || !ws || (P > 0 && (!d_size_idx || !d_es || !d_nes || !d_pval)) || (n_members > 0 && !d_members) || (D > 0 && !d_sizes))
     GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   GsWs w;
-  const size_t need = gs_carve(nullptr, G, C, D, nsim, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  gs_carve((char*)ws, G, C, D, nsim, w);
+  rc = gficf_addon_carve(ws, ws_bytes, [&](char* base) { return gs_carve(base, G, C, D, nsim, w); });
+  if (rc) return rc;
   hipStream_t st = ctx->stream;
   GFICF_HIP_CHECK(hipMemsetAsync(w.status, 0, sizeof(uint32_t), st));
   if (P == 0) return GFICF_OK;
   const int64_t gc = G * C;
-  hipLaunchKernelGGL(k_gs_keys, dim3(gs_grid(gc)), dim3(256), 0, st, gc, d_stats, w.key, w.kv0, w.status);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, 32, w.okey, w.oval);                        // low 32 bits of the key
+  rc = gficf_sort_f64(ctx, w.sort, gc, {d_stats, 1, nullptr, w.status, GS_ST_VALUE, nullptr, nullptr, (uint32_t)G, gficf_bit_width(C - 1)});   // (cluster, statistic desc, row) order
   if (rc) return rc;
-  hipLaunchKernelGGL(k_gs_kv<0>, dim3(gs_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, (const u64*)w.key, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, 32, w.okey, w.oval);                        // high 32 bits
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_gs_kv<1>, dim3(gs_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, (const u64*)w.key, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, gficf_bit_width(C - 1), w.okey, w.oval);    // the cluster, stably
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_gs_rank, dim3(gs_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, w.rank);
+  hipLaunchKernelGGL(k_gs_rank, dim3(gficf_grid_1d(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.sort.oval, w.rank);
   hipLaunchKernelGGL(k_gs_es<false>, dim3((unsigned)(P * C)), dim3(256), 0, st, (int32_t)G, P, D, d_sizes, d_size_idx, d_ptr, n_members, d_members,
                      (const int32_t*)w.rank, (const uint32_t*)nullptr, nsim, (int64_t)0, d_es, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
@@ -370,16 +322,16 @@ int gficf_gsea_device(gficf_ctx* ctx, int64_t G, int32_t C, const double* d_stat
     const int64_t B = gs_batch(G, nsim);
     for (int64_t j0 = 0; j0 < nsim; j0 += B) {
       const int64_t bc = nsim - j0 < B ? nsim - j0 : B;
-      rc = gs_permutations(ctx, w.kv0, w.kv1, w.hist, w.okey, w.oval, G, seed, j0, bc);
+      rc = gs_permutations(ctx, w.sort, G, seed, j0, bc);
       if (rc) return rc;
       hipLaunchKernelGGL(k_gs_es<true>, dim3((unsigned)(D * bc)), dim3(256), 0, st, (int32_t)G, (int64_t)D, D, d_sizes, (const int32_t*)nullptr,
-                         (const int64_t*)nullptr, (int64_t)0, (const int32_t*)nullptr, (const int32_t*)nullptr, (const uint32_t*)w.oval, nsim, j0, null,
+                         (const int64_t*)nullptr, (int64_t)0, (const int32_t*)nullptr, (const int32_t*)nullptr, (const uint32_t*)w.sort.oval, nsim, j0, null,
                          w.status);
       GFICF_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_gs_null_sums, dim3((unsigned)D), dim3(256), 0, st, nsim, (const double*)null, w.nsum);
   }
-  hipLaunchKernelGGL(k_gs_stats, dim3(gs_grid(P * C * 64)), dim3(256), 0, st, P, P * C, D, nsim, d_size_idx, (const double*)null, (const GsNull*)w.nsum,
+  hipLaunchKernelGGL(k_gs_stats, dim3(gficf_grid_1d(P * C * 64)), dim3(256), 0, st, P, P * C, D, nsim, d_size_idx, (const double*)null, (const GsNull*)w.nsum,
                      (const double*)d_es, d_nes, d_pval);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
@@ -458,17 +410,15 @@ int gficf_gsea_permutation_host(gficf_ctx* ctx, int64_t G, uint32_t seed, int64_
   if (G > GFICF_GSEA_MAX_G) GFICF_FAIL(GFICF_ERR_UNSUPPORTED, "G = %lld genes: the LDS gene mask holds %d", (long long)G, GFICF_GSEA_MAX_G);
   gficf_host_io io{ctx, "gficf_gsea_permutation_host"};
   gficf_carver cv;
-  u64 *kv0, *kv1; int64_t* hist; uint32_t *okey, *oval;
+  gficf_sort_bufs s;
   for (int pass = 0; pass < 2 && io.ok(); ++pass) {
-    kv0 = cv.take<u64>((size_t)G + 1); kv1 = cv.take<u64>((size_t)G + 1);
-    hist = cv.take<int64_t>((size_t)gficf_radix_sort_hist_len(G, 32));
-    okey = cv.take<uint32_t>((size_t)G); oval = cv.take<uint32_t>((size_t)G);
+    s.take(cv, 0, (size_t)G, {});                          // no 64-bit keys: one pass over the 32-bit ones
     if (pass == 0) io.e = cv.bind(ctx, GFICF_SLOT_STAGE0);
   }
   int rc = GFICF_OK;
   if (io.ok()) {
-    rc = gs_permutations(ctx, kv0, kv1, hist, okey, oval, G, seed, j, 1);
-    if (!rc) io.down(out, oval, sizeof(int32_t) * (size_t)G);
+    rc = gs_permutations(ctx, s, G, seed, j, 1);
+    if (!rc) io.down(out, s.oval, sizeof(int32_t) * (size_t)G);
   }
   return io.finish(rc);
 }

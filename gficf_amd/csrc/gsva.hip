@@ -13,8 +13,9 @@
 //   k_gv_density     one workgroup per (gene, cluster) segment and range of GFICF_GSVA_JSPLIT entries j: mean, sd, kept, d0,
 //                    and d_j of its j, the segment's x_i staged through LDS in tiles of 256, one x_j per lane
 //   k_gv_gc          G_c, the kept genes of every cluster
-//   k_gv_keys        descending 64-bit key of every d0 (a gene that is not kept sorts last)
-//   3 radix sorts    stable LSD by the key's low 32 bits, its high 32 bits, then the cluster: (cluster, d0 desc, row) order
+//   (addon_sort.h)   k_sort_keys: descending 64-bit key of every d0 (a gene that is not kept sorts last); 3 radix sorts, stable
+//                    LSD by the key's low 32 bits, its high 32 bits, then the cluster (k_sort_next between them): (cluster,
+//                    d0 desc, row) order
 //   k_gv_rank        the rank of every gene in its cluster's order, and the keys in that order
 //   k_gv_sizes       one workgroup per pathway: members checked (range, repeats), m_pc and tested for every cluster
 //   k_gv_walk        one workgroup per cell: its stored kept genes into the two LDS lists (bitonic sort), their positions,
@@ -24,6 +25,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_sort.h"
 #include "addon_status.h"
 #include "common.h"
 #include "gficf_gsva.h"
@@ -43,14 +45,6 @@ constexpr uint32_t GV_ST_PTR = 64u;                   // offsets that decrease o
 constexpr double GV_MIN_SD = 1e-10;
 constexpr double GV_INV_SQRT2 = 0.7071067811865476;
 
-// ascending order of the key = descending order of the value; -0.0 ties with +0.0.  (The key and the gathers between the sort
-// passes below are gsea.hip's scheme, restated here: gsea.o stays built from the source it was tested with.)
-__device__ inline u64 gv_key(double v) {
-  if (v == 0.0) v = 0.0;
-  const u64 b = (u64)__double_as_longlong(v);
-  return ~((b >> 63) ? ~b : (b | (1ull << 63)));
-}
-
 __global__ __launch_bounds__(256) void k_gv_count(int64_t N, int32_t C, const int32_t* __restrict__ cluster, int32_t* __restrict__ n_c,
                                                   uint32_t* __restrict__ status) {
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < N; j += (int64_t)gridDim.x * 256) {
@@ -58,19 +52,6 @@ __global__ __launch_bounds__(256) void k_gv_count(int64_t N, int32_t C, const in
     if (c < 0 || c >= C) atomicOr(status, GV_ST_CLUSTER);
     else atomicAdd(&n_c[c], 1);
   }
-}
-
-// the folded sum of the header: v is thread t's partial sum; every thread gets the total
-__device__ inline double gv_fold(double v, double* s) {
-  const int t = threadIdx.x;
-  __syncthreads();                                         // the previous fold has been read
-  s[t] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (t < h) s[t] += s[t + h];
-    __syncthreads();
-  }
-  return s[0];
 }
 
 // block (s, y): segment s = g * C + c, entries j in [y * JSPLIT, (y + 1) * JSPLIT)
@@ -113,13 +94,13 @@ __global__ __launch_bounds__(256) void k_gv_density(int64_t N, int32_t C, const 
     }
     a += v;
   }
-  const double mean = gv_fold(a, s_fold) / dn;
+  const double mean = gficf_block_sum_f64(a, s_fold) / dn;
   a = 0.0;
   for (int64_t i = t; i < nz; i += 256) {
     const double e = xs[i] - mean;
     a += e * e;
   }
-  const double ss = gv_fold(a, s_fold) + dz * (mean * mean);
+  const double ss = gficf_block_sum_f64(a, s_fold) + dz * (mean * mean);
   const double sdv = n >= 2 ? sqrt(ss / (double)(n - 1)) : 0.0;
   const bool keep = n >= 2 && sdv >= GV_MIN_SD;
   if (!keep) {
@@ -133,7 +114,7 @@ __global__ __launch_bounds__(256) void k_gv_density(int64_t N, int32_t C, const 
     if (nz < n) {
       a = 0.0;
       for (int64_t i = t; i < nz; i += 256) a += 0.5 * erfc(xs[i] * r);
-      const double L0 = (gv_fold(a, s_fold) + 0.5 * dz) / dn;
+      const double L0 = (gficf_block_sum_f64(a, s_fold) + 0.5 * dz) / dn;
       v0 = -log((1.0 - L0) / L0);
     }
     if (t == 0) { sd[out] = sdv; d0[out] = v0; kept[out] = 1; }
@@ -165,35 +146,10 @@ __global__ __launch_bounds__(256) void k_gv_gc(int64_t G, const int32_t* __restr
   const int32_t* col = kept + (int64_t)blockIdx.x * G;
   int32_t cnt = 0;
   for (int64_t g = t; g < G; g += 256) cnt += col[g] != 0 ? 1 : 0;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+  cnt = gficf_wave_sum(cnt);
   if ((t & 63) == 0) s_c[t >> 6] = cnt;
   __syncthreads();
   if (t == 0) gc[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
-
-__global__ __launch_bounds__(256) void k_gv_keys(int64_t n, const double* __restrict__ d0, const int32_t* __restrict__ kept, u64* __restrict__ key,
-                                                 u64* __restrict__ kv, uint32_t* __restrict__ status) {
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
-    u64 k = ~0ull;
-    if (kept[p] != 0) {
-      const double v = d0[p];
-      if (!isfinite(v)) atomicOr(status, GV_ST_VALUE);
-      k = gv_key(v);
-    }
-    key[p] = k;
-    kv[p] = (k << 32) | (u64)p;                            // first pass: the key's low 32 bits
-  }
-}
-
-// next pass: (PART 0: the key's high 32 bits, PART 1: the cluster) << 32 | value, in the order of the previous pass
-template <int PART>
-__global__ __launch_bounds__(256) void k_gv_kv(int64_t n, uint32_t G, const uint32_t* __restrict__ val, const u64* __restrict__ key, u64* __restrict__ kv) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const uint32_t p = val[i];
-    const u64 hi = PART == 0 ? (key[p] >> 32) : (u64)(p / G);
-    kv[i] = (hi << 32) | (u64)p;
-  }
 }
 
 // sorted position i holds val[i] = c * G + g; cluster c fills [c * G, (c + 1) * G)
@@ -238,8 +194,7 @@ __global__ __launch_bounds__(256) void k_gv_sizes(int32_t G, int32_t C, int64_t 
       const int32_t row = members[beg + k];
       if (row >= 0 && row < G) cnt += col[row] != 0 ? 1 : 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+    cnt = gficf_wave_sum(cnt);
     __syncthreads();
     if ((t & 63) == 0) s_c[t >> 6] = cnt;
     __syncthreads();
@@ -249,16 +204,6 @@ __global__ __launch_bounds__(256) void k_gv_sizes(int32_t G, int32_t C, int64_t 
       tested[(int64_t)c * P + p] = (n_c[c] >= 2 && m >= 1 && m >= lo && m <= top) ? 1 : 0;
     }
   }
-}
-
-// the first index of the ascending a[0 .. n) that is not below v
-__device__ inline int gv_lower(const uint32_t* a, int n, uint32_t v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // One workgroup per cell j of cluster c.  LDS lists of the cell's n stored kept genes (dynamic, npad entries each):
@@ -307,7 +252,7 @@ __global__ __launch_bounds__(256) void k_gv_walk(int32_t G, int32_t C, int64_t P
     if (!isfinite(v)) atomicOr(status, GV_ST_VALUE);
     const int i = atomicAdd(&s_n, 1);                      // any slot: the sorts below fix the order (no two entries compare equal)
     A[i] = (uint32_t)rank[cg + g];
-    Bk[i] = gv_key(v);
+    Bk[i] = ~gficf_f64_key(v);                             // descending, as the cluster's order of the d0
     Bg[i] = g;
   }
   __syncthreads();
@@ -345,8 +290,8 @@ __global__ __launch_bounds__(256) void k_gv_walk(int32_t G, int32_t C, int64_t P
       const int32_t gm = (int32_t)((int64_t)order[cg + mid] - cg);
       if (km < kq || (km == kq && gm < g)) lo = mid + 1; else hi = mid;
     }
-    const int ia = gv_lower(A, n, (uint32_t)rank[cg + g]);
-    if (ia < n) posA[ia] = lo - gv_lower(A, n, (uint32_t)lo) + b;
+    const int ia = gficf_lower_bound(A, n, (uint32_t)rank[cg + g]);
+    if (ia < n) posA[ia] = lo - gficf_lower_bound(A, n, (uint32_t)lo) + b;
   }
   __syncthreads();
   const int W = (Gc + 31) >> 5;
@@ -363,12 +308,12 @@ __global__ __launch_bounds__(256) void k_gv_walk(int32_t G, int32_t C, int64_t P
       const int32_t g = members[pb + k];
       if (g < 0 || g >= G || kept[cg + g] == 0) continue;
       const uint32_t r0 = (uint32_t)rank[cg + g];
-      const int ia = gv_lower(A, n, r0);
+      const int ia = gficf_lower_bound(A, n, r0);
       int pos;
       if (ia < n && A[ia] == r0) {
         pos = posA[ia];
       } else {
-        const u64 kq = gv_key(d0[cg + g]);
+        const u64 kq = ~gficf_f64_key(d0[cg + g]);
         int lo = 0, hi = n;
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
@@ -463,9 +408,8 @@ __global__ __launch_bounds__(256) void k_gv_sums(int64_t N, int64_t P, const int
 struct GvWs {
   uint32_t* status;
   int32_t *n_c, *gc;
-  u64 *key, *skey, *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval;
+  gficf_sort_bufs sort;
+  u64* skey;
   int32_t *rank, *msize;
 };
 
@@ -476,21 +420,11 @@ static size_t gv_carve(char* base, int64_t G, int64_t C, int64_t P, GvWs& w) {
   w.status = cv.take<uint32_t>(1);
   w.n_c = cv.take<int32_t>((size_t)C);
   w.gc = cv.take<int32_t>((size_t)C);
-  w.key = cv.take<u64>(gc);
+  w.sort.take(cv, gc, gc, {gficf_bit_width(C - 1)});
   w.skey = cv.take<u64>(gc);
-  w.kv0 = cv.take<u64>(gc + 1);
-  w.kv1 = cv.take<u64>(gc + 1);
-  w.hist = cv.take<int64_t>((size_t)std::max(gficf_radix_sort_hist_len((int64_t)gc, 32), gficf_radix_sort_hist_len((int64_t)gc, gficf_bit_width(C - 1))));
-  w.okey = cv.take<uint32_t>(gc);
-  w.oval = cv.take<uint32_t>(gc);
   w.rank = cv.take<int32_t>(gc);
   w.msize = cv.take<int32_t>((size_t)std::max<int64_t>(P * C, 1));
   return cv.total();
-}
-
-static unsigned gv_grid(int64_t n) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, 256);
-  return (unsigned)(b < 16384 ? b : 16384);
 }
 
 static int gv_check_sizes(int64_t G, int64_t N, int64_t C, int64_t P) {
@@ -505,16 +439,13 @@ static int gv_check_sizes(int64_t G, int64_t N, int64_t C, int64_t P) {
 
 static int gv_workspace(void* ws, size_t ws_bytes, int64_t G, int64_t C, int64_t P, GvWs& w) {
   if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
-  const size_t need = gv_carve(nullptr, G, C, P, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  gv_carve((char*)ws, G, C, P, w);
-  return GFICF_OK;
+  return gficf_addon_carve(ws, ws_bytes, [&](char* base) { return gv_carve(base, G, C, P, w); });
 }
 
 // n_c of every cluster into w.n_c
 static int gv_count(gficf_ctx* ctx, const GvWs& w, int64_t N, int32_t C, const int32_t* d_cluster) {
   GFICF_HIP_CHECK(hipMemsetAsync(w.n_c, 0, sizeof(int32_t) * (size_t)C, ctx->stream));
-  hipLaunchKernelGGL(k_gv_count, dim3(gv_grid(N)), dim3(256), 0, ctx->stream, N, C, d_cluster, w.n_c, w.status);
+  hipLaunchKernelGGL(k_gv_count, dim3(gficf_grid_1d(N)), dim3(256), 0, ctx->stream, N, C, d_cluster, w.n_c, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
 }
@@ -582,19 +513,10 @@ int gficf_gsva_scores_device(gficf_ctx* ctx, int64_t G, int64_t N, int32_t C, co
   if (rc) return rc;
   const int64_t gc = G * C;
   hipLaunchKernelGGL(k_gv_gc, dim3((unsigned)C), dim3(256), 0, st, G, d_kept, w.gc);
-  hipLaunchKernelGGL(k_gv_keys, dim3(gv_grid(gc)), dim3(256), 0, st, gc, d_d0, d_kept, w.key, w.kv0, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, 32, w.okey, w.oval);                        // low 32 bits of the key
+  rc = gficf_sort_f64(ctx, w.sort, gc, {d_d0, 1, d_kept, w.status, GV_ST_VALUE, nullptr, nullptr, (uint32_t)G, gficf_bit_width(C - 1)});   // (cluster, d0 desc, row) order
   if (rc) return rc;
-  hipLaunchKernelGGL(k_gv_kv<0>, dim3(gv_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, (const u64*)w.key, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, 32, w.okey, w.oval);                        // high 32 bits
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_gv_kv<1>, dim3(gv_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, (const u64*)w.key, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, gc, gficf_bit_width(C - 1), w.okey, w.oval);    // the cluster, stably
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_gv_rank, dim3(gv_grid(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.oval, (const u64*)w.key, w.rank, w.skey);
+  hipLaunchKernelGGL(k_gv_rank, dim3(gficf_grid_1d(gc)), dim3(256), 0, st, gc, (uint32_t)G, (const uint32_t*)w.sort.oval, (const u64*)w.sort.key, w.rank, w.skey);
   const int64_t lo = min_size > 1 ? min_size : 1, hi = max_size < G ? max_size : G;
   hipLaunchKernelGGL(k_gv_sizes, dim3((unsigned)P), dim3(256), 0, st, (int32_t)G, C, P, d_ptr, n_members, d_members, d_kept, (const int32_t*)w.n_c,
                      (const int32_t*)w.gc, lo, hi, w.msize, d_tested, w.status);
@@ -604,7 +526,7 @@ int gficf_gsva_scores_device(gficf_ctx* ctx, int64_t G, int64_t N, int32_t C, co
   const size_t lds = (size_t)npad * 20 + (size_t)((G + 31) / 32) * sizeof(uint32_t);
   GFICF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gv_walk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_gv_walk, dim3((unsigned)N), dim3(256), lds, st, (int32_t)G, C, P, (int32_t)npad, d_cluster, d_colptr, d_row, d_src, nnz, d_dnz, d_d0,
-                     d_kept, (const int32_t*)w.gc, (const int32_t*)w.rank, (const u64*)w.skey, (const uint32_t*)w.oval, d_ptr, d_members,
+                     d_kept, (const int32_t*)w.gc, (const int32_t*)w.rank, (const u64*)w.skey, (const uint32_t*)w.sort.oval, d_ptr, d_members,
                      (const int32_t*)w.msize, (const int32_t*)d_tested, d_es, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_gv_sums, dim3((unsigned)gficf_ceil_div(P, 256), (unsigned)C), dim3(256), 0, st, N, P, d_cluster, (const double*)d_es, d_sum, d_sumsq);

@@ -7,7 +7,8 @@
 //   (transpose)       gene-major view of the CSC input (gficf_csc_transpose_device)
 //   k_hv_moments      one wave per gene: nobs, mean, the two-pass sum of squares, lx, ly, valid
 //   k_hv_logs         the same lx, ly, valid from given mean and cv
-//   k_hv_keys, (radix sort x 2), k_hv_kv, k_hv_perm   the stable order of a list of doubles, the invalid ones last
+//   (addon_sort.h: k_sort_keys, k_sort_next<0>, radix sort x 2), k_hv_perm   the stable order of a list of doubles, the
+//                     invalid ones last
 //   k_hv_gather       a list in that order
 //   k_hv_sorted       the check that a list handed in as ascending is
 //   k_hv_locfit       one wave per evaluation point: the window by binary search, eight wave sums, the 3 x 3 solve
@@ -23,56 +24,14 @@
 #include <limits>
 #include <vector>
 
+#include "addon_sort.h"
 #include "addon_status.h"
 #include "common.h"
 #include "gficf_hvg.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr uint32_t HV_ST_ORDER = 1u;                       // a list handed in as ascending decreases (or holds a NaN)
-
-__device__ inline u64 hv_key(double v) {
-  if (v == 0.0) v = 0.0;                                   // -0.0 with +0.0
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
-__device__ inline double hv_wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-__device__ inline int hv_wave_sum_i(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// the folded sum of the header: v is thread t's partial sum; every thread gets the total
-__device__ inline double hv_fold(double v, double* s) {
-  const int t = threadIdx.x;
-  __syncthreads();                                         // the previous fold has been read
-  s[t] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (t < h) s[t] += s[t + h];
-    __syncthreads();
-  }
-  return s[0];
-}
-
-// the first index of the ascending a[0 .. n) with a[i] >= v
-__device__ inline int64_t hv_lower(const double* __restrict__ a, int64_t n, double v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 __device__ inline void hv_logs(double mean, double cv, double* lx, double* ly, int32_t* valid, int64_t g) {
   const double a = log10(mean), b = log10(cv);
@@ -98,15 +57,15 @@ __global__ __launch_bounds__(256) void k_hv_moments(int64_t G, int64_t N, int64_
     const double v = tx[p];
     if (v != 0.0) { a += v; ++cnt; }
   }
-  a = hv_wave_sum(a);
-  cnt = hv_wave_sum_i(cnt);
+  a = gficf_wave_sum(a);
+  cnt = gficf_wave_sum(cnt);
   const double m = a / (double)N;
   double b = 0.0;
   for (int64_t p = beg + lane; p < end; p += 64) {
     const double v = tx[p];
     if (v != 0.0) { const double d = v - m; b += d * d; }
   }
-  b = hv_wave_sum(b);
+  b = gficf_wave_sum(b);
   const double ss = b + (double)(N - cnt) * (m * m);
   const double vr = ss / (double)(N - 1), s = sqrt(vr);
   if (lane == 0) {
@@ -122,26 +81,6 @@ __global__ __launch_bounds__(256) void k_hv_logs(int64_t G, const double* __rest
                                                  double* __restrict__ ly, int32_t* __restrict__ valid) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g < G) hv_logs(mean[g], cv[g], lx, ly, valid, g);
-}
-
-// the sort key of every position (an invalid one: all ones, behind every double), the first pass's elements, the count
-__global__ __launch_bounds__(256) void k_hv_keys(int64_t n, const double* __restrict__ v, const int32_t* __restrict__ valid, u64* __restrict__ key,
-                                                 u64* __restrict__ kv, int32_t* __restrict__ count) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const bool ok = valid == nullptr || valid[i] != 0;
-  const u64 k = ok ? hv_key(v[i]) : ~0ull;
-  key[i] = k;
-  kv[i] = (k << 32) | (u64)i;                              // the key's low 32 bits
-  if (ok) atomicAdd(count, 1);
-}
-
-// second pass: the key's high 32 bits << 32 | position, in the order of the first pass
-__global__ __launch_bounds__(256) void k_hv_kv(int64_t n, const uint32_t* __restrict__ perm, const u64* __restrict__ key, u64* __restrict__ kv) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t p = perm[i];
-  kv[i] = ((key[p] >> 32) << 32) | (u64)p;
 }
 
 __global__ __launch_bounds__(256) void k_hv_perm(int64_t n, const uint32_t* __restrict__ oval, int32_t* __restrict__ perm) {
@@ -225,8 +164,8 @@ __global__ __launch_bounds__(256) void k_hv_locfit(int64_t n, const double* __re
     S0 += ww; S1 += w1; S2 += w2; S3 += w3; S4 += w4;
     T0 += ww * y; T1 += w1 * y; T2 += w2 * y;
   }
-  S0 = hv_wave_sum(S0); S1 = hv_wave_sum(S1); S2 = hv_wave_sum(S2); S3 = hv_wave_sum(S3); S4 = hv_wave_sum(S4);
-  T0 = hv_wave_sum(T0); T1 = hv_wave_sum(T1); T2 = hv_wave_sum(T2);
+  S0 = gficf_wave_sum(S0); S1 = gficf_wave_sum(S1); S2 = gficf_wave_sum(S2); S3 = gficf_wave_sum(S3); S4 = gficf_wave_sum(S4);
+  T0 = gficf_wave_sum(T0); T1 = gficf_wave_sum(T1); T2 = gficf_wave_sum(T2);
   if (lane != 0) return;
   if (hout) hout[e] = h;
   double b0 = nan;
@@ -284,7 +223,7 @@ __global__ __launch_bounds__(256) void k_hv_gap(int64_t n, const double* __restr
   if (i >= len) return;
   const double g = x0 + (double)i * step;
   grid[i] = g;
-  gap[i] = (int32_t)(hv_lower(xs, n, g + half) - hv_lower(xs, n, g - half));
+  gap[i] = (int32_t)(gficf_lower_bound(xs, n, g + half) - gficf_lower_bound(xs, n, g - half));
 }
 
 __global__ __launch_bounds__(256) void k_hv_curve(int64_t len, double x0, double b, double a, double* __restrict__ g1, double* __restrict__ yf) {
@@ -305,7 +244,7 @@ __global__ __launch_bounds__(256) void k_hv_dist(int64_t n, const double* __rest
   const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   if (e >= n) return;                                      // the whole wave
   const double x = lx[e], y = ly[e];
-  const int64_t j0 = hv_lower(g1, len, x - 0.2), j1 = hv_lower(g1, len, x + 0.2);
+  const int64_t j0 = gficf_lower_bound(g1, len, x - 0.2), j1 = gficf_lower_bound(g1, len, x + 0.2);
   double best = __longlong_as_double(0x7ff0000000000000ll);
   int64_t bi = -1;
   for (int64_t j = j0 + lane; j < j1; j += 64) {
@@ -336,10 +275,10 @@ __global__ __launch_bounds__(256) void k_hv_kde_stats(int64_t n, const double* _
   const int t = threadIdx.x;
   double a = 0.0;
   for (int64_t i = t; i < n; i += 256) a += v[i];
-  const double mean = hv_fold(a, s_fold) / (double)n;
+  const double mean = gficf_block_sum_f64(a, s_fold) / (double)n;
   double b = 0.0;
   for (int64_t i = t; i < n; i += 256) { const double d = v[i] - mean; b += d * d; }
-  const double sd = sqrt(hv_fold(b, s_fold) / (double)(n - 1));
+  const double sd = sqrt(gficf_block_sum_f64(b, s_fold) / (double)(n - 1));
   if (t != 0) return;
   double q[2];
   for (int j = 0; j < 2; ++j) {
@@ -380,7 +319,7 @@ __global__ __launch_bounds__(256) void k_hv_kde_dens(int64_t n, const double* __
     const double z = (g - v[i]) / bw;
     a += exp(-0.5 * z * z);
   }
-  const double d = hv_fold(a, s_fold);
+  const double d = gficf_block_sum_f64(a, s_fold);
   if (t == 0) dens[blockIdx.x] = d;
 }
 
@@ -420,9 +359,7 @@ struct HvWs {
   int64_t* tptr;
   int32_t* tidx;
   double* tx;
-  u64 *key, *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval;
+  gficf_sort_bufs sort;
   int32_t *perm, *perm2;
   double *xs, *ys, *w, *fit, *res, *ares, *srt, *cv, *s;
   double *g5, *yseq, *g1, *yf;
@@ -441,12 +378,7 @@ static size_t hv_carve(char* base, int64_t G, int64_t N, int64_t nnz, int64_t gr
   w.tptr = cv.take<int64_t>(N > 0 ? g1 + 1 : 1);
   w.tidx = cv.take<int32_t>(N > 0 ? n1 : 1);
   w.tx = cv.take<double>(N > 0 ? n1 : 1);
-  w.key = cv.take<u64>(g1);
-  w.kv0 = cv.take<u64>(g1 + 1);
-  w.kv1 = cv.take<u64>(g1 + 1);
-  w.hist = cv.take<int64_t>((size_t)gficf_radix_sort_hist_len((int64_t)g1, 32));
-  w.okey = cv.take<uint32_t>(g1);
-  w.oval = cv.take<uint32_t>(g1);
+  w.sort.take(cv, g1, g1, {});
   w.perm = cv.take<int32_t>(g1);
   w.perm2 = cv.take<int32_t>(g1);
   w.xs = cv.take<double>(g1);
@@ -481,30 +413,20 @@ static bool hv_sizes_ok(int64_t G, int64_t N, int64_t nnz, int64_t grid) {
 static int hv_workspace(void* ws, size_t ws_bytes, int64_t n, int64_t N, int64_t nnz, int64_t grid, HvWs& w) {
   if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
   if (!hv_sizes_ok(n, N, nnz, grid)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n = %lld, N = %lld, nnz = %lld, grid = %lld: a size is out of range", (long long)n, (long long)N, (long long)nnz, (long long)grid);
-  const size_t need = hv_carve(nullptr, n, N, nnz, grid, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  hv_carve((char*)ws, n, N, nnz, grid, w);
-  return GFICF_OK;
+  return gficf_addon_carve(ws, ws_bytes, [&](char* base) { return hv_carve(base, n, N, nnz, grid, w); });
 }
 
-// w.oval = the stable ascending order of v[0 .. n) (the invalid last), *count = how many are valid
+// w.sort.oval = the stable ascending order of v[0 .. n) (the invalid last), *count = how many are valid
 static int hv_order(gficf_ctx* ctx, const HvWs& w, int64_t n, const double* d_v, const int32_t* d_valid, int32_t* d_count) {
-  hipStream_t st = ctx->stream;
-  GFICF_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(k_hv_keys, dim3(hv_grid(n)), dim3(256), 0, st, n, d_v, d_valid, w.key, w.kv0, d_count);
-  GFICF_HIP_CHECK(hipGetLastError());
-  int rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, n, 32, w.okey, w.oval);     // low 32 bits of the key
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_hv_kv, dim3(hv_grid(n)), dim3(256), 0, st, n, (const uint32_t*)w.oval, (const u64*)w.key, w.kv0);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, n, 32, w.okey, w.oval);       // high 32 bits
+  GFICF_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int32_t), ctx->stream));
+  return gficf_sort_f64(ctx, w.sort, n, {d_v, 0, d_valid, nullptr, 0u, d_count, nullptr, 0u, 0});
 }
 
 // dst = v ascending (n values, all valid); uses w.perm2
 static int hv_sorted_copy(gficf_ctx* ctx, const HvWs& w, int64_t n, const double* d_v, double* d_dst) {
   int rc = hv_order(ctx, w, n, d_v, nullptr, w.count);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)w.oval, w.perm2);
+  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)w.sort.oval, w.perm2);
   hipLaunchKernelGGL(k_hv_gather, dim3(hv_grid(n)), dim3(256), 0, ctx->stream, n, n, (const int32_t*)w.perm2, d_v, d_dst);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
@@ -685,7 +607,7 @@ static int hv_trend(gficf_ctx* ctx, gficf_host_io& io, const HvWs& w, int64_t G,
   for (int i = 0; i < GFICF_HVG_SCALARS; ++i) o.scalars[i] = nan;
   int rc = hv_order(ctx, w, G, d_lx, d_valid, w.count);
   if (rc) return io.drain(rc);
-  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(G)), dim3(256), 0, st, G, (const uint32_t*)w.oval, w.perm);
+  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(G)), dim3(256), 0, st, G, (const uint32_t*)w.sort.oval, w.perm);
   int32_t n32 = 0;
   std::vector<int32_t> perm((size_t)G);
   io.down(&n32, w.count, sizeof(int32_t));
@@ -821,7 +743,7 @@ int gficf_hvg_order_device(gficf_ctx* ctx, int64_t n, const double* d_key, const
   if (rc) return rc;
   rc = hv_order(ctx, w, n, d_key, d_valid, d_count);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)w.oval, d_perm);
+  hipLaunchKernelGGL(k_hv_perm, dim3(hv_grid(n)), dim3(256), 0, ctx->stream, n, (const uint32_t*)w.sort.oval, d_perm);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
 }

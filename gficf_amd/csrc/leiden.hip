@@ -24,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_ops.h"
 #include "common.h"
 #include "gficf_leiden.h"
 
@@ -100,10 +101,6 @@ template <bool BLK> __device__ inline void ld_clear(int32_t* key, u64* val) {
   for (int i = ld_tid<BLK>(); i < LdShape<BLK>::SLOTS; i += LdShape<BLK>::NT) { key[i] = -1; val[i] = 0; }
 }
 
-__device__ inline u64 ld_wave_sum(u64 x) {
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
 __device__ inline bool ld_better(double g, int32_t c, double bg, int32_t bc) { return c >= 0 && (bc < 0 || g > bg || (g == bg && c < bc)); }
 // best (gain, label) and a sum over the group, the same in every thread; red*: four entries each of the workgroup's LDS
 template <bool BLK>
@@ -113,7 +110,7 @@ __device__ inline void ld_reduce(double& g, int32_t& c, u64& s, double* red_g, i
     const int32_t oc = __shfl_xor(c, d);
     if (ld_better(og, oc, g, c)) { g = og; c = oc; }
   }
-  s = ld_wave_sum(s);
+  s = gficf_wave_sum(s);
   if (BLK) {
     __syncthreads();
     if ((threadIdx.x & 63) == 0) { red_g[threadIdx.x >> 6] = g; red_c[threadIdx.x >> 6] = c; red_s[threadIdx.x >> 6] = s; }
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(256) void k_ld_fix(int64_t N, int64_t nnz, const in
       s += f;
       mx = f > mx ? f : mx;
     }
-    s = ld_wave_sum(s);
+    s = gficf_wave_sum(s);
     if (lane == 0) { kv[v] = s; total += s; }
   }
   for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(mx, d); mx = o > mx ? o : mx; }
@@ -294,21 +291,11 @@ __global__ __launch_bounds__(256) void k_ld_inw(LdG g, const int32_t* __restrict
       if (u == v || comm[u] == cv) s += g.wt[e];
     }
   }
-  s = ld_wave_sum(s);
+  s = gficf_wave_sum(s);
   __shared__ u64 s_sum[4];
   if (lane == 0) s_sum[wave] = s;
   __syncthreads();
   if (threadIdx.x == 0) parts[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-}
-
-__device__ inline double ld_block_sum_f64(double x, double* s_x) {      // a fixed tree: the same bits on every call
-  s_x[threadIdx.x] = x;
-  __syncthreads();
-  for (int d = 128; d >= 1; d >>= 1) {
-    if ((int)threadIdx.x < d) s_x[threadIdx.x] += s_x[threadIdx.x + d];
-    __syncthreads();
-  }
-  return s_x[0];
 }
 
 __global__ __launch_bounds__(256) void k_ld_sq(int64_t n, const u64* __restrict__ K, double* __restrict__ parts) {
@@ -318,7 +305,7 @@ __global__ __launch_bounds__(256) void k_ld_sq(int64_t n, const u64* __restrict_
     const double k = (double)K[c];
     x += k * k;
   }
-  x = ld_block_sum_f64(x, s_x);
+  x = gficf_block_sum_f64(x, s_x);
   if (threadIdx.x == 0) parts[blockIdx.x] = x;
 }
 
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(256) void k_ld_qfin(int nb_in, const u64* __restric
   for (int i = threadIdx.x; i < nb_in; i += 256) a += pin[i];
   for (int i = threadIdx.x; i < nb_sq; i += 256) x += psq[i];
   s_i[threadIdx.x] = a;
-  x = ld_block_sum_f64(x, s_x);
+  x = gficf_block_sum_f64(x, s_x);
   if (threadIdx.x == 0) {
     u64 t = 0;
     for (int i = 0; i < 256; ++i) t += s_i[i];
@@ -367,7 +354,7 @@ __global__ __launch_bounds__(256) void k_rf_ext(LdG g, int first, const int32_t*
       const int32_t u = g.nbr[e];
       if (u != v && comm[u] == cv && ref[u] != rv) s += g.wt[e];
     }
-    s = ld_wave_sum(s);
+    s = gficf_wave_sum(s);
     if (lane == 0) {
       if (first) { ec[v] = s; ext[v] = s; }
       else if (s) atomicAdd(&ext[rv], s);

@@ -7,8 +7,10 @@
 // into one tie group whose rank follows from counts.  Launches:
 //   k_mk_labels     cluster sizes, labels outside [0, C) flagged
 //   (transpose)     gene-major view of the CSC input (gficf_csc_transpose_device), cells ascending within a gene
-//   k_mk_keys       order-preserving 64-bit key of every value (-0.0 -> +0.0; NaN / Inf flagged), gene of every entry
-//   3 radix sorts   stable LSD by the key's low 32 bits, its high 32 bits, then the gene: (gene, value) order
+//   k_mk_gene_of    gene of every entry
+//   (addon_sort.h)  k_sort_keys: order-preserving 64-bit key of every value (-0.0 -> +0.0; NaN / Inf flagged); 3 radix sorts,
+//                   stable LSD by the key's low 32 bits, its high 32 bits, then the gene (k_sort_next between them): (gene,
+//                   value) order
 //   k_mk_heads      sorted keys and cluster ids gathered, tie-group heads marked; (scan) -> group numbers
 //   k_mk_bounds     first and one-past-last sorted position of every tie group
 //   k_mk_walk       one workgroup per gene: 2 * rank, count and 128-bit fixed-point value sum per cluster (LDS while
@@ -19,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "addon_sort.h"
 #include "addon_status.h"
 #include "common.h"
 #include "gficf_markers.h"
@@ -42,12 +45,7 @@ struct MkGene {                           // per-gene results of the walk
   int32_t k, f64;                         // f64: k < MK_FIXED_MIN_K, the accumulators hold f64 sums (cluster in lo, rest in hi)
 };
 
-__device__ inline u64 mk_key(double v) {
-  if (v == 0.0) v = 0.0;                                   // -0.0 ties with +0.0, as the reference's < and != have it
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
+// the value of a key of gficf_f64_key (whose -0.0 ties with +0.0, as the reference's < and != have it)
 __device__ inline double mk_value(u64 key) {
   return __longlong_as_double((long long)((key >> 63) ? (key & ~(1ull << 63)) : ~key));
 }
@@ -93,28 +91,6 @@ __global__ __launch_bounds__(256) void k_mk_gene_of(int64_t G, int64_t nnz, cons
     for (int64_t p = tptr[g] + lane; p < tptr[g + 1] && p < nnz; p += 64) gene[p] = (uint32_t)g;
 }
 
-__global__ __launch_bounds__(256) void k_mk_keys(int64_t nnz, const double* __restrict__ x, u64* __restrict__ key, u64* __restrict__ kv,
-                                                 uint32_t* __restrict__ status) {
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * 256) {
-    const double v = x[p];
-    if (!isfinite(v)) atomicOr(status, MK_ST_VALUE);
-    const u64 k = mk_key(v);
-    key[p] = k;
-    kv[p] = (k << 32) | (u64)p;                            // first pass: the key's low 32 bits
-  }
-}
-
-// next pass: element (part of the key or the gene) << 32 | position, in the order of the previous pass
-template <int PART>
-__global__ __launch_bounds__(256) void k_mk_kv(int64_t nnz, const uint32_t* __restrict__ perm, const u64* __restrict__ key,
-                                               const uint32_t* __restrict__ gene, u64* __restrict__ kv) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * 256) {
-    const uint32_t p = perm[i];
-    const u64 hi = PART == 0 ? (key[p] >> 32) : (u64)gene[p];
-    kv[i] = (hi << 32) | (u64)p;
-  }
-}
-
 // sorted keys and cluster ids; head[i] = 1 where a tie group (of one gene) starts; head[nnz] = 0
 __global__ __launch_bounds__(256) void k_mk_heads(int64_t nnz, int64_t N, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ gene_s,
                                                   const u64* __restrict__ key, const int32_t* __restrict__ tidx, const int32_t* __restrict__ cluster,
@@ -137,12 +113,6 @@ __global__ __launch_bounds__(256) void k_mk_bounds(int64_t nnz, const int64_t* _
     if (g1 - e[i] == 1) gstart[g1 - 1] = (uint32_t)i;
     if (i == nnz - 1 || e[i + 2] - g1 == 1) gend[g1 - 1] = (uint32_t)(i + 1);
   }
-}
-
-__device__ inline int64_t mk_wave_sum(int64_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 // accumulators of gene g, C wide: r2 (sum of 2 * rank over the cluster's non-zero entries), cnt (its non-zero entries),
@@ -201,7 +171,7 @@ __global__ __launch_bounds__(256) void k_mk_walk(int64_t G, int64_t N, int nb, i
       if (v < 0.0) ++neg; else ++pos;
       if (i == s) { t3 += t * t * t - t; ++nd; }
     }
-    neg = mk_wave_sum(neg); pos = mk_wave_sum(pos); t3 = mk_wave_sum(t3); nd = mk_wave_sum(nd);
+    neg = gficf_wave_sum(neg); pos = gficf_wave_sum(pos); t3 = gficf_wave_sum(t3); nd = gficf_wave_sum(nd);
     u64 tlo = (u64)tot, thi = (u64)((unsigned __int128)tot >> 64);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -338,9 +308,8 @@ struct MkWs {
   int64_t* tptr;
   int32_t* tidx;
   double* tx;
-  u64 *key, *kv0, *kv1;
-  int64_t* hist;
-  uint32_t *okey, *oval, *gene, *cls, *gstart, *gend;
+  gficf_sort_bufs sort;
+  uint32_t *gene, *cls, *gstart, *gend;
   MkGene* gst;
   u64 *r2, *cnt, *lo, *hi;
 };
@@ -356,13 +325,7 @@ static size_t mk_carve(char* base, int64_t G, int64_t N, int64_t nnz, int64_t C,
   w.tptr = cv.take<int64_t>((size_t)G + 1);
   w.tidx = cv.take<int32_t>(n1);
   w.tx = cv.take<double>(n1);
-  w.key = cv.take<u64>(n1);
-  w.kv0 = cv.take<u64>(n1 + 1);
-  w.kv1 = cv.take<u64>(n1 + 1);
-  const int64_t h32 = gficf_radix_sort_hist_len(nnz, 32), hg = gficf_radix_sort_hist_len(nnz, gficf_bit_width(G));
-  w.hist = cv.take<int64_t>((size_t)(h32 > hg ? h32 : hg));
-  w.okey = cv.take<uint32_t>(n1);
-  w.oval = cv.take<uint32_t>(n1);
+  w.sort.take(cv, n1, n1, {gficf_bit_width(G)});
   w.gene = cv.take<uint32_t>(n1);
   w.cls = cv.take<uint32_t>(n1);
   w.gstart = cv.take<uint32_t>(n1);
@@ -373,11 +336,6 @@ static size_t mk_carve(char* base, int64_t G, int64_t N, int64_t nnz, int64_t C,
   w.lo = cv.take<u64>(gc);
   w.hi = cv.take<u64>(gc);
   return cv.total();
-}
-
-static unsigned mk_grid(int64_t n) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, 256);
-  return (unsigned)(b < 16384 ? b : 16384);
 }
 
 static int mk_check_sizes(int64_t G, int64_t N, int64_t nnz, int64_t C) {
@@ -394,44 +352,36 @@ static int mk_check_sizes(int64_t G, int64_t N, int64_t nnz, int64_t C) {
 static int mk_core(gficf_ctx* ctx, const MkWs& w, int64_t G, int64_t N, int64_t nnz, const int32_t* d_cluster, int32_t C, double* d_p,
                    double* d_lfc) {
   hipStream_t st = ctx->stream;
+  const gficf_sort_bufs& s = w.sort;
   if (nnz > 0) {
-    hipLaunchKernelGGL(k_mk_gene_of, dim3(mk_grid(G * 64)), dim3(256), 0, st, G, nnz, (const int64_t*)w.tptr, w.gene);
-    hipLaunchKernelGGL(k_mk_keys, dim3(mk_grid(nnz)), dim3(256), 0, st, nnz, (const double*)w.tx, w.key, w.kv0, w.status);
+    hipLaunchKernelGGL(k_mk_gene_of, dim3(gficf_grid_1d(G * 64)), dim3(256), 0, st, G, nnz, (const int64_t*)w.tptr, w.gene);
     GFICF_HIP_CHECK(hipGetLastError());
-    int rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, nnz, 32, w.okey, w.oval);               // low 32 bits of the key
+    int rc = gficf_sort_f64(ctx, s, nnz, {w.tx, 0, nullptr, w.status, MK_ST_VALUE, nullptr, w.gene, 0u, gficf_bit_width(G)});   // (gene, value) order
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mk_kv<0>, dim3(mk_grid(nnz)), dim3(256), 0, st, nnz, (const uint32_t*)w.oval, (const u64*)w.key, (const uint32_t*)w.gene, w.kv0);
-    GFICF_HIP_CHECK(hipGetLastError());
-    rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, nnz, 32, w.okey, w.oval);                   // high 32 bits
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_mk_kv<1>, dim3(mk_grid(nnz)), dim3(256), 0, st, nnz, (const uint32_t*)w.oval, (const u64*)w.key, (const uint32_t*)w.gene, w.kv0);
-    GFICF_HIP_CHECK(hipGetLastError());
-    rc = gficf_radix_sort_kv(ctx, w.kv0, w.kv1, w.hist, nnz, gficf_bit_width(G), w.okey, w.oval);   // the gene, stably
-    if (rc) return rc;
-    int64_t* const head = (int64_t*)w.kv1;
-    hipLaunchKernelGGL(k_mk_heads, dim3(mk_grid(nnz + 1)), dim3(256), 0, st, nnz, N, (const uint32_t*)w.oval, (const uint32_t*)w.okey, (const u64*)w.key,
-                       (const int32_t*)w.tidx, d_cluster, w.kv0, w.cls, head);
+    int64_t* const head = (int64_t*)s.kv1;
+    hipLaunchKernelGGL(k_mk_heads, dim3(gficf_grid_1d(nnz + 1)), dim3(256), 0, st, nnz, N, (const uint32_t*)s.oval, (const uint32_t*)s.okey, (const u64*)s.key,
+                       (const int32_t*)w.tidx, d_cluster, s.kv0, w.cls, head);
     GFICF_HIP_CHECK(hipGetLastError());
     rc = gficf_exclusive_scan_i64(ctx, head, nnz + 1);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mk_bounds, dim3(mk_grid(nnz)), dim3(256), 0, st, nnz, (const int64_t*)head, w.gstart, w.gend);
+    hipLaunchKernelGGL(k_mk_bounds, dim3(gficf_grid_1d(nnz)), dim3(256), 0, st, nnz, (const int64_t*)head, w.gstart, w.gend);
     GFICF_HIP_CHECK(hipGetLastError());
   }
   const unsigned wg = (unsigned)(G < (1 << 20) ? (G > 0 ? G : 1) : (1 << 20));
   if (C <= MK_LDS_MAX_C) {
-    hipLaunchKernelGGL(k_mk_walk<true>, dim3(wg), dim3(256), (size_t)C * 4 * sizeof(u64), st, G, N, gficf_bit_width(N), nnz, C, (const int64_t*)w.tptr, (const u64*)w.kv0,
-                       (const uint32_t*)w.cls, (const int64_t*)w.kv1, (const uint32_t*)w.gstart, (const uint32_t*)w.gend, w.r2, w.cnt, w.lo, w.hi, w.gst);
+    hipLaunchKernelGGL(k_mk_walk<true>, dim3(wg), dim3(256), (size_t)C * 4 * sizeof(u64), st, G, N, gficf_bit_width(N), nnz, C, (const int64_t*)w.tptr, (const u64*)s.kv0,
+                       (const uint32_t*)w.cls, (const int64_t*)s.kv1, (const uint32_t*)w.gstart, (const uint32_t*)w.gend, w.r2, w.cnt, w.lo, w.hi, w.gst);
   } else {
     const size_t gc = (size_t)G * (size_t)C * sizeof(u64);
     GFICF_HIP_CHECK(hipMemsetAsync(w.r2, 0, gc, st));
     GFICF_HIP_CHECK(hipMemsetAsync(w.cnt, 0, gc, st));
     GFICF_HIP_CHECK(hipMemsetAsync(w.lo, 0, gc, st));
     GFICF_HIP_CHECK(hipMemsetAsync(w.hi, 0, gc, st));
-    hipLaunchKernelGGL(k_mk_walk<false>, dim3(wg), dim3(256), 0, st, G, N, gficf_bit_width(N), nnz, C, (const int64_t*)w.tptr, (const u64*)w.kv0, (const uint32_t*)w.cls,
-                       (const int64_t*)w.kv1, (const uint32_t*)w.gstart, (const uint32_t*)w.gend, w.r2, w.cnt, w.lo, w.hi, w.gst);
+    hipLaunchKernelGGL(k_mk_walk<false>, dim3(wg), dim3(256), 0, st, G, N, gficf_bit_width(N), nnz, C, (const int64_t*)w.tptr, (const u64*)s.kv0, (const uint32_t*)w.cls,
+                       (const int64_t*)s.kv1, (const uint32_t*)w.gstart, (const uint32_t*)w.gend, w.r2, w.cnt, w.lo, w.hi, w.gst);
   }
   GFICF_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_mk_epilogue, dim3(mk_grid(G * C)), dim3(256), 0, st, G, N, C, (const u64*)w.ncl, (const u64*)w.r2, (const u64*)w.cnt,
+  hipLaunchKernelGGL(k_mk_epilogue, dim3(gficf_grid_1d(G * C)), dim3(256), 0, st, G, N, C, (const u64*)w.ncl, (const u64*)w.r2, (const u64*)w.cnt,
                      (const u64*)w.lo, (const u64*)w.hi, (const MkGene*)w.gst, d_p, d_lfc, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
@@ -470,12 +420,11 @@ int gficf_cluster_markers_device(gficf_ctx* ctx, int64_t G, int64_t N, const int
   if (!d_colptr || !d_cluster || !ws || (G > 0 && (!d_p || !d_lfc)) || (nnz > 0 && (!d_rowidx || !d_x)))
     GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   MkWs w;
-  const size_t need = mk_carve(nullptr, G, N, nnz, C, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  mk_carve((char*)ws, G, N, nnz, C, w);
+  rc = gficf_addon_carve(ws, ws_bytes, [&](char* base) { return mk_carve(base, G, N, nnz, C, w); });
+  if (rc) return rc;
   GFICF_HIP_CHECK(hipMemsetAsync(w.status, 0, sizeof(uint32_t), ctx->stream));
   GFICF_HIP_CHECK(hipMemsetAsync(w.ncl, 0, sizeof(u64) * (size_t)C, ctx->stream));
-  hipLaunchKernelGGL(k_mk_labels, dim3(mk_grid(N)), dim3(256), 0, ctx->stream, N, d_cluster, C, w.ncl, w.status);
+  hipLaunchKernelGGL(k_mk_labels, dim3(gficf_grid_1d(N)), dim3(256), 0, ctx->stream, N, d_cluster, C, w.ncl, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
   if (G == 0) return GFICF_OK;
   rc = gficf_csc_transpose_device(ctx, G, N, d_colptr, d_rowidx, d_x, nnz, w.tptr, w.tidx, w.tx, w.tr_ws, w.tr_bytes);
@@ -558,7 +507,7 @@ int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, cons
   io.up(dY, Y, sizeof(double) * (size_t)(G * n2));
   if (!io.ok()) return io.drain(GFICF_OK);
   GFICF_HIP_CHECK(hipMemsetAsync(cnt + G * nch, 0, sizeof(int64_t), st));
-  hipLaunchKernelGGL(k_mk_dense<false>, dim3(mk_grid(G * nch)), dim3(256), 0, st, G, n1, n2, dX, dY, nch, cnt, (int32_t*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL(k_mk_dense<false>, dim3(gficf_grid_1d(G * nch)), dim3(256), 0, st, G, n1, n2, dX, dY, nch, cnt, (int32_t*)nullptr, (double*)nullptr);
   GFICF_HIP_CHECK(hipGetLastError());
   rc = gficf_exclusive_scan_i64(ctx, cnt, G * nch + 1);
   if (rc) return rc;
@@ -572,9 +521,9 @@ int gficf_cluster_markers_dense_host(gficf_ctx* ctx, int64_t G, int64_t n1, cons
   mk_carve((char*)wsp, G, N, nnz, 2, w);
   GFICF_HIP_CHECK(hipMemsetAsync(w.status, 0, sizeof(uint32_t), st));
   GFICF_HIP_CHECK(hipMemsetAsync(w.ncl, 0, sizeof(u64) * 2, st));
-  hipLaunchKernelGGL(k_mk_dense<true>, dim3(mk_grid(G * nch)), dim3(256), 0, st, G, n1, n2, dX, dY, nch, cnt, w.tidx, w.tx);
-  hipLaunchKernelGGL(k_mk_dense_ptr, dim3(mk_grid((G > N ? G : N) + 1)), dim3(256), 0, st, G, nch, n1, N, (const int64_t*)cnt, w.tptr, dcl);
-  hipLaunchKernelGGL(k_mk_labels, dim3(mk_grid(N)), dim3(256), 0, st, N, (const int32_t*)dcl, 2, w.ncl, w.status);
+  hipLaunchKernelGGL(k_mk_dense<true>, dim3(gficf_grid_1d(G * nch)), dim3(256), 0, st, G, n1, n2, dX, dY, nch, cnt, w.tidx, w.tx);
+  hipLaunchKernelGGL(k_mk_dense_ptr, dim3(gficf_grid_1d((G > N ? G : N) + 1)), dim3(256), 0, st, G, nch, n1, N, (const int64_t*)cnt, w.tptr, dcl);
+  hipLaunchKernelGGL(k_mk_labels, dim3(gficf_grid_1d(N)), dim3(256), 0, st, N, (const int32_t*)dcl, 2, w.ncl, w.status);
   GFICF_HIP_CHECK(hipGetLastError());
   rc = mk_core(ctx, w, G, N, nnz, dcl, 2, dp, dl);
   if (!rc) {                                     // out = [p, log2FC] of the first sample (cluster 0): column 0 of each G x 2 result

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "addon_status.h"
+#include "block_ops.h"
 #include "common.h"
 #include "gficf_tmm.h"
 
@@ -38,61 +39,12 @@ __device__ inline int64_t tm_at(const void* p, int is64, int64_t i) {
   return is64 ? ((const int64_t*)p)[i] : (int64_t)((const int32_t*)p)[i];
 }
 
-// the folded sum of the header: v is thread t's partial sum; every thread gets the total
-__device__ inline double tm_fold(double v, double* s) {
-  const int t = threadIdx.x;
-  __syncthreads();                                         // the previous fold has been read
-  s[t] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (t < h) s[t] += s[t + h];
-    __syncthreads();
-  }
-  return s[0];
-}
-
-__device__ inline double tm_fold_max(double v, double* s) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  s[t] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (t < h) s[t] = fmax(s[t], s[t + h]);
-    __syncthreads();
-  }
-  return s[0];
-}
-
-// ascending bitonic sort of the np2 (a power of two) keys of a[] by the whole workgroup
-__device__ inline void tm_sort(u64* a, int np2) {
-  for (int k = 2; k <= np2; k <<= 1) {
-    for (int h = k >> 1; h > 0; h >>= 1) {
-      for (int i = threadIdx.x; i < np2; i += 256) {
-        const int l = i ^ h;
-        if (l > i) {
-          const u64 a0 = a[i], a1 = a[l];
-          if ((a0 > a1) == ((i & k) == 0)) { a[i] = a1; a[l] = a0; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// the average rank of v among the ascending a[0 .. n), v one of them: #less + (#equal + 1) / 2
+// the average rank of v among the ascending a[0 .. n), v one of them: #less + (#equal + 1) / 2.  The keys are the bits of
+// doubles that are not negative (the sign bit is clear), so v + 1 does not wrap: the first key above v is the first not below it.
 __device__ inline double tm_rank(const u64* a, int n, u64 v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  const int less = lo;
-  hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] <= v) lo = mid + 1; else hi = mid;
-  }
-  return (double)less + (double)(lo - less + 1) / 2.0;
+  const int less = gficf_lower_bound(a, n, v);
+  const int equal = gficf_lower_bound(a + less, n - less, v + 1);
+  return (double)less + (double)(equal + 1) / 2.0;
 }
 
 __global__ __launch_bounds__(256) void k_tm_rows(int64_t G, int64_t nnz, const int32_t* __restrict__ row, const double* __restrict__ x,
@@ -145,7 +97,7 @@ __global__ __launch_bounds__(256) void k_tm_stats(int64_t N, const void* __restr
       if (i < cap) keys[i] = (u64)__double_as_longlong(v);
     }
   }
-  const double L = tm_fold(a, s_fold), S = tm_fold(b, s_fold);
+  const double L = gficf_block_sum_f64(a, s_fold), S = gficf_block_sum_f64(b, s_fold);
   const int64_t npos = s_n, Gp = gp[0];
   double q = 0.0, xlo = 0.0, xhi = 0.0;
   if (Gp > 0) {
@@ -159,7 +111,7 @@ __global__ __launch_bounds__(256) void k_tm_stats(int64_t N, const void* __restr
         while (np2 < npos) np2 <<= 1;
         for (int i = (int)npos + t; i < np2; i += 256) keys[i] = ~0ull;
         __syncthreads();
-        tm_sort(keys, np2);
+        gficf_lds_sort_u64(keys, np2);
         if (t == 0) {
           s_res[0] = klo >= 0 ? __longlong_as_double((long long)keys[klo]) : 0.0;
           s_res[1] = __longlong_as_double((long long)keys[khi]);
@@ -245,7 +197,7 @@ __device__ inline void tm_term(double obs, double r, double rq, double rs, const
 __device__ inline void tm_finish(int64_t c, int n, double num, double den, int kept, double mx, double* s_fold, int32_t* s_kept,
                                  double* __restrict__ factor, int32_t* __restrict__ n_out, int32_t* __restrict__ kept_out) {
 #pragma clang fp contract(off)
-  const double A = tm_fold(num, s_fold), B = tm_fold(den, s_fold), M = tm_fold_max(mx, s_fold);
+  const double A = gficf_block_sum_f64(num, s_fold), B = gficf_block_sum_f64(den, s_fold), M = gficf_block_max_f64(mx, s_fold);
   atomicAdd(s_kept, kept);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -324,8 +276,8 @@ __device__ inline void tm_cell(int64_t c, const void* __restrict__ colptr, int i
   while (np2 < n) np2 <<= 1;
   for (int i = n + t; i < np2; i += 256) { Kq[i] = ~0ull; Ks[i] = ~0ull; }
   __syncthreads();
-  tm_sort(Kq, np2);
-  tm_sort(Ks, np2);
+  gficf_lds_sort_u64(Kq, np2);
+  gficf_lds_sort_u64(Ks, np2);
   tm_bounds(n, A.lt, A.st, b);
   double num = 0.0, den = 0.0;
   int kept = 0;
@@ -474,11 +426,6 @@ static size_t tm_carve(char* base, int64_t G, int64_t N, int64_t big_cells, int6
   return cv.total();
 }
 
-static unsigned tm_grid(int64_t n) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, 256);
-  return (unsigned)(b < 16384 ? b : 16384);
-}
-
 static int tm_check_sizes(int64_t G, int64_t N, int64_t nnz, int64_t max_cell_nz, int64_t max_lds_n) {
   if (G < 1 || N < 1 || nnz < 0 || max_cell_nz < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "G = %lld, N = %lld, nnz = %lld, max_cell_nz = %lld: a size is out of range", (long long)G, (long long)N, (long long)nnz, (long long)max_cell_nz);
   if (G > INT32_MAX || N > INT32_MAX) GFICF_FAIL(GFICF_ERR_UNSUPPORTED, "more than 2^31 - 1 genes or cells");
@@ -490,10 +437,7 @@ static int tm_check_sizes(int64_t G, int64_t N, int64_t nnz, int64_t max_cell_nz
 static int tm_workspace(void* ws, size_t ws_bytes, int64_t G, int64_t N, int64_t big_cells, int64_t big_entries, TmWs& w) {
   if (!ws) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL workspace");
   if (big_cells < 0 || big_entries < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "big_cells = %lld, big_entries = %lld", (long long)big_cells, (long long)big_entries);
-  const size_t need = tm_carve(nullptr, G, N, big_cells, big_entries, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  tm_carve((char*)ws, G, N, big_cells, big_entries, w);
-  return GFICF_OK;
+  return gficf_addon_carve(ws, ws_bytes, [&](char* base) { return tm_carve(base, G, N, big_cells, big_entries, w); });
 }
 
 // the LDS list length (a power of two, at least 64) and the capacity the kernels keep to, from the caller's bounds
@@ -530,7 +474,7 @@ int gficf_tmm_stats_device(gficf_ctx* ctx, int64_t G, int64_t N, const void* d_c
   hipStream_t st = ctx->stream;
   GFICF_HIP_CHECK(hipMemsetAsync(w.status, 0, sizeof(uint32_t), st));
   GFICF_HIP_CHECK(hipMemsetAsync(w.flag, 0, sizeof(int32_t) * (size_t)G, st));
-  hipLaunchKernelGGL(k_tm_rows, dim3(tm_grid(nnz)), dim3(256), 0, st, G, nnz, d_rowidx, d_x, w.flag, w.status);
+  hipLaunchKernelGGL(k_tm_rows, dim3(gficf_grid_1d(nnz)), dim3(256), 0, st, G, nnz, d_rowidx, d_x, w.flag, w.status);
   hipLaunchKernelGGL(k_tm_gp, dim3(1), dim3(256), 0, st, G, (const int32_t*)w.flag, w.gp, d_gprime);
   GFICF_HIP_CHECK(hipGetLastError());
   int32_t cap, npad;
@@ -564,7 +508,7 @@ int gficf_tmm_factors_device(gficf_ctx* ctx, int64_t G, int64_t N, const void* d
   GFICF_HIP_CHECK(hipMemsetAsync(w.mid_cnt, 0, sizeof(uint32_t), st));
   GFICF_HIP_CHECK(hipMemsetAsync(w.cursor, 0, sizeof(u64), st));
   GFICF_HIP_CHECK(hipMemsetAsync(w.ref, 0, sizeof(double) * (size_t)G, st));
-  hipLaunchKernelGGL(k_tm_ref, dim3(tm_grid(std::min(max_cell_nz, G))), dim3(256), 0, st, G, d_colptr, colptr_is_i64, ref_col, nnz, d_rowidx, d_x, w.ref);
+  hipLaunchKernelGGL(k_tm_ref, dim3(gficf_grid_1d(std::min(max_cell_nz, G))), dim3(256), 0, st, G, d_colptr, colptr_is_i64, ref_col, nnz, d_rowidx, d_x, w.ref);
   GFICF_HIP_CHECK(hipGetLastError());
   int32_t cap, npad;
   tm_lds_shape(max_cell_nz, max_lds_n, &cap, &npad);

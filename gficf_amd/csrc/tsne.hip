@@ -23,6 +23,7 @@
 
 #include "addon_kernels.h"
 #include "addon_status.h"
+#include "block_ops.h"
 #include "common.h"
 #include "gficf_tsne.h"
 #include "knn_symmetrise.h"
@@ -56,24 +57,11 @@ TsShape ts_shape(int64_t N) {
   return s;
 }
 
-// the sum of one value per lane of a 256-lane workgroup, the same tree whatever the values; every lane gets it
-__device__ inline double ts_block_sum(double v, double* sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
-
-// the sum of n values: lane t adds the values t, t + 256, .. in order, then the tree
+// the sum of n values: lane t adds the values t, t + 256, .. in order, then the fixed tree of block_ops.h
 __device__ inline double ts_strided_sum(const double* __restrict__ v, int64_t n, double* sh) {
   double s = 0.0;
   for (int64_t t = threadIdx.x; t < n; t += 256) s += v[t];
-  return ts_block_sum(s, sh);
+  return gficf_block_sum_f64(s, sh);
 }
 
 // ------------------------------------------------------------------------------------------------ affinities: beta, Pc
@@ -223,7 +211,7 @@ __global__ __launch_bounds__(256) void k_ts_repulse(const float2* __restrict__ Y
       zl += az[r];
     }
   }
-  const double zb = ts_block_sum(zl, red);
+  const double zb = gficf_block_sum_f64(zl, red);
   if (threadIdx.x == 0) zpart[rb * gridDim.y + s] = zb;
 }
 
@@ -324,7 +312,7 @@ __global__ __launch_bounds__(256) void k_ts_centre(const float2* __restrict__ Yn
   __shared__ double red[256];
   double sx = 0.0, sy = 0.0;
   for (int64_t t = threadIdx.x; t < nparts; t += 256) { sx += ypart[2 * t]; sy += ypart[2 * t + 1]; }
-  const double mx = ts_block_sum(sx, red) / (double)N, my = ts_block_sum(sy, red) / (double)N;
+  const double mx = gficf_block_sum_f64(sx, red) / (double)N, my = gficf_block_sum_f64(sy, red) / (double)N;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const float2 y = Ynew[i];

@@ -1,6 +1,8 @@
 """Builds tests/helpers/prim_probe.hip against gficf_amd/csrc/common.h into tests/helpers/libprim_probe.so (linked to
 libgficf_hip.so) and binds it with ctypes: the radix sort, the int64 exclusive scan and the scan epoch of a context, which
-the library keeps internal (the exported gficf_* surface is pinned by tests/test_abi.py).  Test infrastructure only."""
+the library keeps internal (the exported gficf_* surface is pinned by tests/test_abi.py), and the header-only code the add-ons
+share (block_ops.h, addon_sort.h): the grouped f64 sort, the block sum and max, the LDS sort and the lower bound.  Test
+infrastructure only."""
 from __future__ import annotations
 
 import ctypes
@@ -14,10 +16,12 @@ SRC = os.path.join(HERE, "prim_probe.hip")
 SO = os.path.join(HERE, "libprim_probe.so")
 LIBDIR = os.path.join(ROOT, "gficf_amd")
 CSRC = os.path.join(LIBDIR, "csrc")
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "gficf_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "block_ops.h"), os.path.join(CSRC, "addon_sort.h"),
+           os.path.join(ROOT, "include", "gficf_hip.h")]
 
 SYMBOLS = ["probe_radix_sort_kv", "probe_radix_sort_hist_len", "probe_exclusive_scan_i64", "probe_get_scan_epoch",
-           "probe_set_scan_epoch", "probe_ctx_sync"]
+           "probe_set_scan_epoch", "probe_ctx_sync", "probe_sort_f64", "probe_block_ops", "probe_lds_sort_u64",
+           "probe_lower_bound_f64", "probe_lower_bound_u32"]
 
 
 def hipcc() -> str | None:
@@ -63,6 +67,11 @@ class Probe:
             ("probe_get_scan_epoch", u32, [vp]),
             ("probe_set_scan_epoch", None, [vp, u32]),
             ("probe_ctx_sync", ci, [vp]),
+            ("probe_sort_f64", ci, [vp, vp, i64, vp, ci, vp, vp, u32, vp, vp, u32, ci, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+            ("probe_block_ops", ci, [vp, vp, vp, i64, vp]),
+            ("probe_lds_sort_u64", ci, [vp, vp, ci, i64]),
+            ("probe_lower_bound_f64", ci, [vp, vp, i64, vp, i64, vp]),
+            ("probe_lower_bound_u32", ci, [vp, vp, ci, vp, i64, vp]),
         ]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
@@ -84,3 +93,28 @@ class Probe:
 
     def sync(self, ctx) -> int:
         return self.L.probe_ctx_sync(ctx)
+
+    def sort_f64_bytes(self, n, group_bits) -> int:
+        """The block gficf_sort_bufs::take asks for: n elements, one group width (0: none)."""
+        total = ctypes.c_int64(0)
+        assert self.L.probe_sort_f64(None, None, int(n), None, 0, None, None, 0, None, None, 0, int(group_bits), None, ctypes.byref(total)) == 0
+        return total.value
+
+    def sort_f64(self, ctx, ws, n, v, desc, mask, status, st_bit, count, group, G, group_bits):
+        """Enqueues the sort; returns (rc, the byte offsets of key, kv0, kv1, hist, okey, oval in ws)."""
+        offs, total = (ctypes.c_int64 * 6)(), ctypes.c_int64(0)
+        rc = self.L.probe_sort_f64(ctx, ws, int(n), v, int(desc), mask, status, int(st_bit), count, group, int(G), int(group_bits), offs,
+                                   ctypes.byref(total))
+        return rc, list(offs)
+
+    def block_ops(self, ctx, a, b, nblocks, out) -> int:
+        return self.L.probe_block_ops(ctx, a, b, int(nblocks), out)
+
+    def lds_sort(self, ctx, data, np2, nblocks) -> int:
+        return self.L.probe_lds_sort_u64(ctx, data, int(np2), int(nblocks))
+
+    def lower_f64(self, ctx, a, n, q, m, out) -> int:
+        return self.L.probe_lower_bound_f64(ctx, a, int(n), q, int(m), out)
+
+    def lower_u32(self, ctx, a, n, q, m, out) -> int:
+        return self.L.probe_lower_bound_u32(ctx, a, int(n), q, int(m), out)

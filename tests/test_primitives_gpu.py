@@ -7,8 +7,13 @@
   transpose    gficf_csc_transpose (transpose.hip): pairing (G <= 9000), plain with one gene range and with several
                (G > 36864), the cells-per-block floor of 16 and cap of 1024, long cells, empty cells and genes, explicit zeros
 
-The sort and the scan are reached through tests/helpers/prim_probe.py; references are exact (NumPy / torch stable sorts and
-integer cumulative sums)."""
+  f64 sort     gficf_sort_f64 (addon_sort.h): the add-ons' stable sort of doubles within groups against numpy.lexsort, every
+               form of its first pass (descending, mask, status, count) and of its groups (none, array, divisor), the
+               buffers carved by gficf_sort_bufs::take, nothing written outside them
+  block ops    block_ops.h: the folded sum and max against the same tree in NumPy, bit for bit; the LDS sort; the lower bound
+
+The sort, the scan and the add-ons' headers are reached through tests/helpers/prim_probe.py; references are exact (NumPy /
+torch stable sorts, integer cumulative sums, the same float64 additions in the same order)."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -315,3 +320,191 @@ def test_transpose_cells_per_block_cap(G, N):
     cp, ri, x = _random_csc(G, N, 2_500_000, seed=N, long_cells=[(N - 1, 3000), (N // 2, 1100)], empty_cells=(1, 2, N - 2),
                             empty_genes=(5,), zeros_every=29)
     _check_transpose(G, N, cp, ri, x, ops)
+
+
+# ------------------------------------------------------------------------------------------------ what the add-ons share
+# block_ops.h and addon_sort.h are header-only: the probe compiles them as the add-ons do.
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _bit_width(n):
+    """gficf_bit_width: the smallest b in 1..32 with 2^b > n."""
+    return max(1, int(n).bit_length())
+
+
+def _sort_values(n, rng, inf=True):
+    """n doubles without a NaN: both zeros, both infinities, denormals, many exact duplicates, pairs whose keys differ in the
+    low 32 bits only and pairs whose keys differ in the high 32 bits only (what a dropped or swapped pass gets wrong)."""
+    base = rng.standard_normal(24) * 10.0 ** rng.integers(-6, 7, 24)
+    bits = base.view(np.uint64)
+    hi, lo = bits >> np.uint64(32), rng.integers(0, 2 ** 32, 24, dtype=np.uint64)
+    low_pairs = np.concatenate([(hi << np.uint64(32)) | lo, (hi << np.uint64(32)) | (lo ^ np.uint64(0x80000001))]).view(np.float64)
+    high_pairs = np.concatenate([(hi << np.uint64(32)) | lo[0], (np.roll(hi, 1) << np.uint64(32)) | lo[0]]).view(np.float64)
+    special = [0.0, -0.0, 5e-324, -5e-324, 1.1e-308, -3.3e-310, 1.7976931348623157e308] + ([np.inf, -np.inf] if inf else [])
+    first = [0, 24, 1, 25, 2, 26]                           # three pairs of either kind ahead, for the smallest n
+    pool = np.concatenate([np.array(special), low_pairs[first], high_pairs[first], low_pairs, high_pairs, base[:6], -base[:6]])
+    assert not np.isnan(pool).any()
+    if n < 8:
+        return rng.choice(np.array(special), n)
+    body = np.concatenate([pool, rng.choice(pool, max(n - 4 - len(pool), 0))])[:n - 4]
+    if n > 600:
+        body[len(pool)::3] = rng.standard_normal(len(body[len(pool)::3]))     # distinct values among the duplicates
+    return np.concatenate([[0.0, -0.0, -0.0, 0.0], rng.permutation(body)])    # the zeros must tie and keep this order
+
+
+def _expected_order(v, desc, mask, group):
+    """numpy.lexsort on (group, masked-out last, value, original position); -0.0 is +0.0, a masked-out value does not count."""
+    x = v + 0.0 if mask is None else np.where(mask != 0, v + 0.0, 0.0)
+    keys = [np.arange(len(v)), -x if desc else x]
+    keys.append(np.zeros(len(v), dtype=np.int8) if mask is None else (mask == 0).astype(np.int8))
+    keys.append(np.zeros(len(v), dtype=np.int64) if group is None else group.astype(np.int64))
+    return np.lexsort(tuple(keys))
+
+
+def _f64_sort_and_check(probe, ctx, v, desc, mask=None, group=None, G=0, group_bits=0, status_bit=0, want_status=0):
+    n = len(v)
+    total = probe.sort_f64_bytes(n, group_bits)
+    ws = torch.full((total,), 0x5A, dtype=torch.uint8, device=DEV)
+    d_v, d_mask = _dev(v), None if mask is None else _dev(mask.astype(np.int32))
+    d_group = None if group is None or G else _dev(group.astype(np.uint32).view(np.int32))
+    status = torch.tensor([0, CANARY], dtype=torch.int32, device=DEV)
+    count = torch.tensor([0, CANARY], dtype=torch.int32, device=DEV)
+    torch.cuda.synchronize()
+    rc, offs = probe.sort_f64(ctx, _ptr(ws), n, _ptr(d_v), desc, _ptr(d_mask), _ptr(status) if status_bit else None, status_bit, _ptr(count),
+                              _ptr(d_group), G, group_bits)
+    assert rc == OK and probe.sync(ctx) == OK
+    order = _expected_order(v, desc, mask, group)
+    o_key, _, _, o_hist, o_okey, o_oval = offs
+    oval = ws[o_oval:o_oval + 4 * n].view(torch.int32).cpu().numpy().view(np.uint32)
+    assert np.array_equal(oval, order.astype(np.uint32)), (n, desc, group_bits)
+    if group is not None:
+        okey = ws[o_okey:o_okey + 4 * n].view(torch.int32).cpu().numpy().view(np.uint32)
+        assert np.array_equal(okey, group[order].astype(np.uint32)), (n, desc, group_bits)
+    key = ws[o_key:o_key + 8 * n].view(torch.int64).cpu().numpy().view(np.uint64)
+    kept = np.ones(n, dtype=bool) if mask is None else mask != 0
+    assert (key[~kept] == np.uint64(2 ** 64 - 1)).all() and (key[kept] != np.uint64(2 ** 64 - 1)).all()
+    assert count.tolist() == [int(kept.sum()), CANARY] and status.tolist() == [want_status, CANARY]
+    assert np.array_equal(d_v.cpu().numpy().view(np.uint64), v.view(np.uint64))            # the input is left alone
+    # nothing written outside the six buffers: n elements each (the + 1 of kv0 / kv1 is not the sort's), the histogram as
+    # long as the widest pass asks
+    hl = max(probe.hist_len(n, 32), probe.hist_len(n, group_bits) if group_bits else 0)
+    used = torch.zeros(total, dtype=torch.bool, device=DEV)
+    for off, size in zip(offs, (8 * n, 8 * n, 8 * n, 8 * hl, 4 * n, 4 * n)):
+        assert off % 256 == 0 and off + size <= total
+        used[off:off + size] = True
+    assert bool((ws[~used] == 0x5A).all()), (n, desc, group_bits)
+
+
+SORT_N = [1, 2, 255, 256, 257, 4096, 4097, 70_001]
+
+
+@pytest.mark.parametrize("n", SORT_N)
+def test_f64_sort_against_lexsort(probe, ctx, n):
+    """Ascending and descending; no group and group by array, its width as markers.hip computes it (gficf_bit_width(G))."""
+    rng = np.random.default_rng(n)
+    v = _sort_values(n, rng)
+    Gn = max(1, n // 14)                                    # 70 001: 5000 groups, 13 bits, two digit passes
+    group = rng.integers(0, Gn, n)
+    for desc in (0, 1):
+        _f64_sort_and_check(probe, ctx, v, desc)
+        _f64_sort_and_check(probe, ctx, v, desc, group=group, group_bits=_bit_width(Gn))
+
+
+@pytest.mark.parametrize("C", [1, 5])
+def test_f64_sort_group_by_divisor(probe, ctx, C):
+    """n = G C statistics, entry p in group p / G, G = 37: the width as gsea.hip and gsva.hip compute it (gficf_bit_width(C - 1))."""
+    G = 37
+    rng = np.random.default_rng(100 + C)
+    v = _sort_values(G * C, rng)
+    group = np.arange(G * C) // G
+    mask = (rng.random(G * C) < 0.7).astype(np.int32)
+    for desc in (0, 1):
+        _f64_sort_and_check(probe, ctx, v, desc, group=group, G=G, group_bits=_bit_width(C - 1))
+        _f64_sort_and_check(probe, ctx, v, desc, mask=mask, group=group, G=G, group_bits=_bit_width(C - 1))
+
+
+@pytest.mark.parametrize("n", SORT_N)
+def test_f64_sort_mask_status_count(probe, ctx, n):
+    """Masked-out entries come last in input order (within their group) and are not counted; one infinity raises the status
+    bit and the order is still right; an infinity that is masked out is not looked at."""
+    rng = np.random.default_rng(1000 + n)
+    v = _sort_values(n, rng, inf=False)
+    mask = (rng.random(n) < 0.6).astype(np.int32)
+    group = rng.integers(0, 3, n)
+    for desc in (0, 1):
+        _f64_sort_and_check(probe, ctx, v, desc, mask=mask, status_bit=4, want_status=0)
+        _f64_sort_and_check(probe, ctx, v, desc, mask=mask, group=group, group_bits=_bit_width(3), status_bit=4, want_status=0)
+    w = v.copy()
+    w[n // 2] = np.inf
+    m = mask.copy()
+    m[n // 2] = 1
+    _f64_sort_and_check(probe, ctx, w, 0, status_bit=4, want_status=4)
+    _f64_sort_and_check(probe, ctx, w, 1, mask=m, status_bit=2, want_status=2)
+    m[n // 2] = 0
+    _f64_sort_and_check(probe, ctx, w, 1, mask=m, status_bit=2, want_status=0)
+
+
+def test_block_sum_and_max_are_the_fixed_tree(probe, ctx):
+    """256 partials over 30 orders of magnitude with mixed signs: any other order of the additions gives other bits.  Sum and
+    max, each twice back to back through one LDS buffer, in 300 workgroups."""
+    nb = 300
+    rng = np.random.default_rng(7)
+    a, b = (rng.choice([-1.0, 1.0], (nb, 256)) * 10.0 ** rng.uniform(-15, 15, (nb, 256)) for _ in range(2))
+    out = torch.full((4 * nb + 16,), -7.0, dtype=torch.float64, device=DEV)
+    d_a, d_b = _dev(a), _dev(b)
+    torch.cuda.synchronize()
+    assert probe.block_ops(ctx, _ptr(d_a), _ptr(d_b), nb, _ptr(out)) == OK and probe.sync(ctx) == OK
+
+    def tree(x):
+        s = x.copy()
+        h = 128
+        while h >= 1:
+            s[:, :h] = s[:, :h] + s[:, h:2 * h]
+            h >>= 1
+        return s[:, 0]
+
+    got = out[:4 * nb].cpu().numpy().reshape(nb, 4)
+    for j, want in enumerate((tree(a), tree(b), a.max(axis=1), b.max(axis=1))):
+        assert np.array_equal(got[:, j].view(np.uint64), want.view(np.uint64)), j
+    assert (np.sort(a, axis=1).sum(axis=1) != tree(a)).any()           # the inputs do tell the orders apart
+    assert bool((out[4 * nb:] == -7.0).all())
+
+
+@pytest.mark.parametrize("np2", [2, 64, 256, 512, 2048, 8192])
+def test_lds_sort_u64(probe, ctx, np2):
+    nb = 5
+    rng = np.random.default_rng(np2)
+    x = rng.integers(0, 2 ** 64, (nb, np2), dtype=np.uint64)
+    x[:, ::3] = rng.choice(x[0, :4], x[:, ::3].shape)       # duplicates
+    x[1, np2 // 2:] = np.uint64(2 ** 64 - 1)                # the padding the callers add
+    x[2, 1:] = np.uint64(2 ** 64 - 1)
+    x[3] = np.sort(x[3])[::-1]
+    d = torch.cat([_dev(x.view(np.int64)).reshape(-1), torch.full((64,), CANARY, dtype=torch.int64, device=DEV)])
+    torch.cuda.synchronize()
+    assert probe.lds_sort(ctx, _ptr(d), np2, nb) == OK and probe.sync(ctx) == OK
+    got = d[:nb * np2].cpu().numpy().view(np.uint64).reshape(nb, np2)
+    assert np.array_equal(got, np.sort(x, axis=1))
+    assert bool((d[nb * np2:] == CANARY).all())
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 1000])
+def test_lower_bound(probe, ctx, n):
+    """double / int64 and uint32 / int: below the first, above the last, at and next to every distinct value."""
+    rng = np.random.default_rng(n + 11)
+    a64 = np.sort(rng.choice(rng.standard_normal(max(n // 3, 1)) * 100.0, n))              # duplicates
+    a32 = np.sort(rng.choice(rng.integers(1, 2 ** 32 - 1, max(n // 3, 1), dtype=np.uint32), n))   # both halves of the range
+    for a, lower, one in ((a64, probe.lower_f64, None), (a32, probe.lower_u32, np.uint32(1))):
+        d = np.unique(a)
+        if one is None:
+            q = np.concatenate([d, np.nextafter(d, -np.inf), np.nextafter(d, np.inf), [-1e300, 1e300, 0.0]])
+            out = torch.full((len(q) + 16,), -7, dtype=torch.int64, device=DEV)
+            d_a, d_q = _dev(a), _dev(q)
+        else:
+            q = np.concatenate([d, d - one, d + one, np.array([0, 2 ** 32 - 1], dtype=np.uint32)]).astype(np.uint32)
+            out = torch.full((len(q) + 16,), -7, dtype=torch.int32, device=DEV)
+            d_a, d_q = _dev(a.view(np.int32)), _dev(q.view(np.int32))
+        torch.cuda.synchronize()
+        assert lower(ctx, _ptr(d_a), n, _ptr(d_q), len(q), _ptr(out)) == OK and probe.sync(ctx) == OK
+        assert np.array_equal(out[:len(q)].cpu().numpy(), np.searchsorted(a, q, side="left"))
+        assert bool((out[len(q):] == -7).all())
