@@ -1,5 +1,6 @@
 // block_ops.h — the device inlines the statistics add-ons (markers, gsea, gsva, tmm, hvg) and tsne, leiden share: wave and
-// workgroup reductions, the LDS sort, the search and the sort key of a double; and the capped 1-D grid of their launches.
+// workgroup reductions, the LDS sort, the search and the sort key of a double; and the capped 1-D grid of their launches (and,
+// through community_ops.h, of louvain.hip's).
 // Inlines only, no kernel: including it emits nothing (the kernels of the 64-bit-key sort are in addon_sort.h).  Every
 // workgroup function is for 256 threads and is reached by all of them.
 #pragma once
@@ -76,8 +77,11 @@ __device__ inline gficf_u64 gficf_f64_key(double v) {
   return (b >> 63) ? ~b : (b | (1ull << 63));
 }
 
-// workgroups of 256 threads for n items, at most 16384: the kernels launched with it are grid-stride
-inline unsigned gficf_grid_1d(int64_t n) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, 256);
-  return (unsigned)(b < 16384 ? b : 16384);
+// workgroups for n items at `per` a workgroup: at least one, at most cap (a kernel whose grid the cap can cut is grid-stride)
+inline unsigned gficf_grid_capped(int64_t n, int64_t per, unsigned cap) {
+  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, per);
+  return (unsigned)(b < (int64_t)cap ? b : (int64_t)cap);
 }
+
+// workgroups of 256 threads for n items, at most 16384: the kernels launched with it are grid-stride
+inline unsigned gficf_grid_1d(int64_t n) { return gficf_grid_capped(n, 256, 16384); }

@@ -172,6 +172,13 @@ void gficf_set_error(const char* fmt, ...);
     }                                                                                      \
   } while (0)
 
+// a step's status code, if it is not GFICF_OK, ends the function that ran the step
+#define GFICF_RC(expr)         \
+  do {                         \
+    const int _rc = (expr);    \
+    if (_rc) return _rc;       \
+  } while (0)
+
 // Binds the calling thread to the context's device.
 #define GFICF_CTX_ENTER(ctx)                                         \
   do {                                                               \

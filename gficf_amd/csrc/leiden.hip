@@ -5,7 +5,7 @@
 // Launches (n vertices of a level; "w/b" = a wave-per-vertex launch for rows up to 128 entries and, only where the level has a
 // longer row, a workgroup-per-vertex launch for those):
 //   once             k_ld_fix (fixed-point weights, diagonal zeroed, vertex weights, 2W, validation), k_ld_check_labels
-//   per iteration    k_ld_first + k_ld_canon (a community's label = its smallest member), k_ld_iota (the vertex map)
+//   per iteration    k_ld_first + k_ld_canon (a community's label = its smallest member), k_comm_iota (the vertex map)
 //   per level        k_ld_accum (totals and sizes of the start partition), the quality launches (below)
 //     per pass       3 copies (the undo snapshot); per sub-round (4): k_ld_move w/b, k_ld_apply; then the quality launches
 //                    k_ld_inw (internal weight, per-block integer partial sums), k_ld_sq (sum K^2 over fixed chunks),
@@ -16,7 +16,7 @@
 //     aggregation    k_ld_flag_ref + scan (new ids), k_ag_vertex (k, row capacities, community of a new vertex), scan (row
 //                    starts), k_ag_emit w/b, k_ag_finish, k_ag_comm, k_ag_top
 //   at the end       k_ld_gather (labels of the finest vertices), canon, k_ld_accum + quality (Q of the result),
-//                    k_ld_size_keys, radix sort, k_ld_rank, k_ld_final
+//                    the numbering by size of community_ops.h (k_comm_size_keys, radix sort, k_comm_rank, k_comm_final)
 // No floating-point atomics; the integer atomics are on per-community totals (distinct addresses); "something moved" is a word
 // every mover stores 1 into, not a counter.
 #include <cmath>
@@ -24,15 +24,14 @@
 #include <cstring>
 #include <vector>
 
-#include "block_ops.h"
 #include "common.h"
+#include "community_ops.h"
 #include "gficf_leiden.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr double LD_SCALE = 4294967296.0;     // 2^32
 constexpr int LD_SMALL_DEG = 128;             // up to here: one wave per vertex, 256-slot table
 constexpr int LD_SMALL_SLOTS = 256;
 constexpr int LD_BIG_SLOTS = 4096;            // beyond: one workgroup per vertex, 16 KB keys + 32 KB sums
@@ -56,16 +55,6 @@ struct LdG {
   const u64* kv;
 };
 
-__device__ __host__ inline uint32_t ld_hash(uint32_t v) {
-  v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
-  return v;
-}
-
-inline unsigned ld_blocks(int64_t n, int per, unsigned cap) {
-  const int64_t b = gficf_ceil_div(n > 0 ? n : 1, per);
-  return (unsigned)(b < (int64_t)cap ? b : (int64_t)cap);
-}
-
 // ---------------------------------------------------------------- the LDS table of a vertex's neighbouring communities
 template <bool BLK> struct LdShape {
   static constexpr int SLOTS = BLK ? LD_BIG_SLOTS : LD_SMALL_SLOTS;
@@ -85,18 +74,8 @@ template <bool BLK> __device__ inline int ld_passes(int64_t deg, int64_t n) {
   const int64_t d = deg < n ? deg : n;
   return (int)((d + LD_PASS_KEYS - 1) / LD_PASS_KEYS);
 }
-__device__ inline bool ld_in_pass(int32_t c, int P, int p) { return P == 1 || (int)((ld_hash((uint32_t)c) >> 12) % (uint32_t)P) == p; }
+__device__ inline bool ld_in_pass(int32_t c, int P, int p) { return P == 1 || (int)((gficf_comm_hash((uint32_t)c) >> 12) % (uint32_t)P) == p; }
 
-template <int SLOTS>
-__device__ inline bool ld_insert(int32_t* key, u64* val, int32_t c, u64 w) {
-  unsigned h = ld_hash((uint32_t)c) & (SLOTS - 1);
-  for (int i = 0; i < SLOTS; ++i) {
-    const int32_t old = atomicCAS(&key[h], -1, c);
-    if (old == -1 || old == c) { atomicAdd(&val[h], w); return true; }
-    h = (h + 1) & (SLOTS - 1);
-  }
-  return false;
-}
 template <bool BLK> __device__ inline void ld_clear(int32_t* key, u64* val) {
   for (int i = ld_tid<BLK>(); i < LdShape<BLK>::SLOTS; i += LdShape<BLK>::NT) { key[i] = -1; val[i] = 0; }
 }
@@ -140,7 +119,7 @@ __global__ __launch_bounds__(256) void k_ld_fix(int64_t N, int64_t nnz, const in
       const double w = x[e];
       const bool idok = u >= 0 && u < N, ok = idok && w >= 0.0 && w <= 1048576.0;      // NaN fails the comparisons
       if (!ok) atomicOr(status, idok ? LD_ST_VALUE : LD_ST_CSC);
-      const u64 f = ok && u != v ? (u64)llrint(w * LD_SCALE) : 0ull;
+      const u64 f = ok && u != v ? (u64)llrint(w * GFICF_COMM_SCALE) : 0ull;
       wt[e] = f;
       s += f;
       mx = f > mx ? f : mx;
@@ -165,14 +144,6 @@ __global__ __launch_bounds__(256) void k_ld_check_labels(int64_t N, const int32_
   if (v < N && (lab[v] < 0 || lab[v] >= N)) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_ID);
 }
 
-__global__ __launch_bounds__(256) void k_ld_fill32(int64_t n, int32_t value, int32_t* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < n) out[v] = value;
-}
-__global__ __launch_bounds__(256) void k_ld_iota(int64_t n, int32_t* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < n) out[v] = (int32_t)v;
-}
 // first[c] = the smallest member of c (an integer minimum: the order does not matter)
 __global__ __launch_bounds__(256) void k_ld_first(int64_t n, const int32_t* __restrict__ lab, int32_t* __restrict__ first) {
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -214,7 +185,7 @@ __global__ __launch_bounds__(256) void k_ld_move(LdG g, double r, int s, int t, 
   for (int64_t v = ld_first_vertex<BLK>(); v < g.n; v += ld_vertex_stride<BLK>()) {
     const int64_t lo = g.beg[v], hi = g.end[v];
     if ((hi - lo > LD_SMALL_DEG) != BLK) continue;
-    const bool run = (int)(ld_hash((uint32_t)v ^ hseed) % (uint32_t)LD_SUB) == s && (t <= LD_SUB || mark[v] >= t - LD_SUB);
+    const bool run = (int)(gficf_comm_hash((uint32_t)v ^ hseed) % (uint32_t)LD_SUB) == s && (t <= LD_SUB || mark[v] >= t - LD_SUB);
     if (!run) {
       if (tid == 0) next[v] = -1;
       continue;
@@ -235,7 +206,8 @@ __global__ __launch_bounds__(256) void k_ld_move(LdG g, double r, int s, int t, 
         const int32_t c = comm[u];
         if (c == cv) { if (p == 0) stay += w; continue; }
         if (!ld_in_pass(c, P, p)) continue;
-        if (!ld_insert<SH::SLOTS>(key, val, c, w)) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
+        bool own;      // (who claimed the slot: not needed here)
+        if (gficf_comm_insert<SH::SLOTS>(key, val, c, w, &own) < 0) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
       }
       ld_sync<BLK>();
       for (int i = tid; i < SH::SLOTS; i += SH::NT) {
@@ -400,7 +372,8 @@ __global__ __launch_bounds__(256) void k_rf_propose(LdG g, double r, const int32
         if (u == v || w == 0 || comm[u] != cv) continue;
         const int32_t ru = ref[u];
         if (!ld_in_pass(ru, P, p)) continue;
-        if (!ld_insert<SH::SLOTS>(key, val, ru, w)) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
+        bool own;      // (who claimed the slot: not needed here)
+        if (gficf_comm_insert<SH::SLOTS>(key, val, ru, w, &own) < 0) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
       }
       ld_sync<BLK>();
       for (int i = tid; i < SH::SLOTS; i += SH::NT) {
@@ -474,7 +447,8 @@ __global__ __launch_bounds__(256) void k_ag_emit(LdG g, const int32_t* __restric
         if (w == 0) continue;
         const int32_t c = (int32_t)newid[ref[g.nbr[e]]];
         if (!ld_in_pass(c, P, p)) continue;
-        if (!ld_insert<SH::SLOTS>(key, val, c, w)) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
+        bool own;      // (who claimed the slot: not needed here)
+        if (gficf_comm_insert<SH::SLOTS>(key, val, c, w, &own) < 0) atomicOr((uint32_t*)(scal + LD_S_STATUS), LD_ST_DENSE);
       }
       ld_sync<BLK>();
       // every wave places the slots of its 64-slot chunks: one reservation in the row per wave
@@ -515,20 +489,6 @@ __global__ __launch_bounds__(256) void k_ag_top(int64_t N, int32_t* __restrict__
   if (v < N) top[v] = (int32_t)newid[ref[top[v]]];
 }
 
-// ---------------------------------------------------------------- final numbering: clusters by decreasing size, ties by first vertex
-__global__ __launch_bounds__(256) void k_ld_size_keys(int64_t n, const int32_t* __restrict__ size, u64* __restrict__ kv) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c < n) kv[c] = ((u64)(n - size[c]) << 32) | (u64)c;      // an unused label sorts last
-}
-__global__ __launch_bounds__(256) void k_ld_rank(int64_t n, const uint32_t* __restrict__ sorted_ids, int32_t* __restrict__ rank) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) rank[sorted_ids[p]] = (int32_t)p;
-}
-__global__ __launch_bounds__(256) void k_ld_final(int64_t n, const int32_t* __restrict__ lab, const int32_t* __restrict__ rank, int32_t* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (v < n) out[v] = rank[lab[v]];
-}
-
 // ---------------------------------------------------------------- host side
 struct LdLevel { int64_t* beg; int64_t* end; int32_t* nbr; u64* wt; u64* kv; };
 struct LdWs {
@@ -538,7 +498,7 @@ struct LdWs {
   u64 *K, *snapK, *Kr, *ext, *ec, *cur;
   int64_t *flag, *newid;
   u64* pin; double* psq;
-  u64* skv[2]; int64_t* shist; uint32_t *skey, *sid;
+  gficf_comm_sort_bufs sort;
   u64* scal;
 };
 
@@ -557,8 +517,7 @@ size_t ld_carve(LdWs* w, void* base, int64_t N, int64_t nnz) {
   for (u64** p : i64) *p = b.take<u64>(n);
   d.flag = b.take<int64_t>(n + 1); d.newid = b.take<int64_t>(n + 1);
   d.pin = b.take<u64>(LD_PARTS); d.psq = b.take<double>(LD_PARTS);
-  d.skv[0] = b.take<u64>(n); d.skv[1] = b.take<u64>(n); d.skey = b.take<uint32_t>(n); d.sid = b.take<uint32_t>(n);
-  d.shist = b.take<int64_t>((size_t)gficf_radix_sort_hist_len((int64_t)n, gficf_bit_width(N > 0 ? N : 1)));
+  d.sort.take(b, n, N > 0 ? N : 1);
   d.scal = b.take<u64>(LD_S_N);
   if (w) *w = d;
   return b.total();
@@ -574,12 +533,6 @@ struct LdRun {
   hipStream_t st() const { return ctx->stream; }
 };
 
-#define LD_RC(expr)            \
-  do {                         \
-    const int _rc = (expr);    \
-    if (_rc) return _rc;       \
-  } while (0)
-
 int ld_read_scal(LdRun& R, u64* h) {
   GFICF_HIP_CHECK(hipMemcpyAsync(h, R.w.scal, sizeof(u64) * LD_S_N, hipMemcpyDeviceToHost, R.st()));
   GFICF_HIP_CHECK(hipStreamSynchronize(R.st()));
@@ -591,10 +544,10 @@ int ld_read_scal(LdRun& R, u64* h) {
 int ld_setup(LdRun& R, const int64_t* d_indptr, const int32_t* d_indices, const double* d_x, const int32_t* d_labels, bool* no_edges) {
   LdWs& w = R.w;
   GFICF_HIP_CHECK(hipMemsetAsync(w.scal, 0, sizeof(u64) * LD_S_N, R.st()));
-  hipLaunchKernelGGL(k_ld_fix, dim3(ld_blocks(R.N, 4, 2048)), dim3(256), 0, R.st(), R.N, R.nnz, d_indptr, d_indices, d_x, w.wt0, w.kv0, w.scal);
-  if (d_labels) hipLaunchKernelGGL(k_ld_check_labels, dim3(ld_blocks(R.N, 256, 1u << 30)), dim3(256), 0, R.st(), R.N, d_labels, w.scal);
+  hipLaunchKernelGGL(k_ld_fix, dim3(gficf_grid_capped(R.N, 4, 2048)), dim3(256), 0, R.st(), R.N, R.nnz, d_indptr, d_indices, d_x, w.wt0, w.kv0, w.scal);
+  if (d_labels) hipLaunchKernelGGL(k_ld_check_labels, dim3(gficf_grid_capped(R.N, 256, 1u << 30)), dim3(256), 0, R.st(), R.N, d_labels, w.scal);
   u64 h[LD_S_N];
-  LD_RC(ld_read_scal(R, h));
+  GFICF_RC(ld_read_scal(R, h));
   const uint32_t status = (uint32_t)h[LD_S_STATUS];
   if (status & LD_ST_CSC) GFICF_FAIL(GFICF_ERR_BAD_CSC, "malformed matrix: a row pointer that is not monotone within [0, nnz] or an index outside [0, N)");
   if (status & LD_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "an edge weight that is not finite or outside [0, 2^20]");
@@ -611,8 +564,8 @@ int ld_setup(LdRun& R, const int64_t* d_indptr, const int32_t* d_indices, const 
 
 // out[v] = the smallest member of lab[v]'s community (out may be lab)
 void ld_canon(LdRun& R, const int32_t* lab, int32_t* out) {
-  const unsigned gb = ld_blocks(R.N, 256, 1u << 30);
-  hipLaunchKernelGGL(k_ld_fill32, dim3(gb), dim3(256), 0, R.st(), R.N, INT32_MAX, R.w.first);
+  const unsigned gb = gficf_grid_capped(R.N, 256, 1u << 30);
+  hipLaunchKernelGGL(k_comm_fill<int32_t>, dim3(gb), dim3(256), 0, R.st(), R.N, INT32_MAX, R.w.first);
   hipLaunchKernelGGL(k_ld_first, dim3(gb), dim3(256), 0, R.st(), R.N, lab, R.w.first);
   hipLaunchKernelGGL(k_ld_canon, dim3(gb), dim3(256), 0, R.st(), R.N, lab, (const int32_t*)R.w.first, out);
 }
@@ -620,17 +573,17 @@ void ld_canon(LdRun& R, const int32_t* lab, int32_t* out) {
 int ld_accum(LdRun& R, const LdG& g, const int32_t* comm) {
   GFICF_HIP_CHECK(hipMemsetAsync(R.w.K, 0, sizeof(u64) * (size_t)g.n, R.st()));
   GFICF_HIP_CHECK(hipMemsetAsync(R.w.size, 0, sizeof(int32_t) * (size_t)g.n, R.st()));
-  hipLaunchKernelGGL(k_ld_accum, dim3(ld_blocks(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, comm, g.kv, R.w.K, R.w.size);
+  hipLaunchKernelGGL(k_ld_accum, dim3(gficf_grid_capped(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, comm, g.kv, R.w.K, R.w.size);
   return GFICF_OK;
 }
 
 // Q of (comm, K) on g; synchronises.  h: the scalar block as read (the "moved" word among it)
 int ld_quality(LdRun& R, const LdG& g, const int32_t* comm, double* q, u64* h) {
-  const unsigned gi = ld_blocks(g.n, 4, LD_PARTS), gs = ld_blocks(g.n, 256, LD_PARTS);
+  const unsigned gi = gficf_grid_capped(g.n, 4, LD_PARTS), gs = gficf_grid_capped(g.n, 256, LD_PARTS);
   hipLaunchKernelGGL(k_ld_inw, dim3(gi), dim3(256), 0, R.st(), g, comm, R.w.pin);
   hipLaunchKernelGGL(k_ld_sq, dim3(gs), dim3(256), 0, R.st(), g.n, (const u64*)R.w.K, R.w.psq);
   hipLaunchKernelGGL(k_ld_qfin, dim3(1), dim3(256), 0, R.st(), (int)gi, (const u64*)R.w.pin, (int)gs, (const double*)R.w.psq, R.w.scal);
-  LD_RC(ld_read_scal(R, h));
+  GFICF_RC(ld_read_scal(R, h));
   double sq;
   memcpy(&sq, &h[LD_S_SQ], sizeof(double));
   *q = (double)h[LD_S_INW] / R.two_w - R.resolution * sq / (R.two_w * R.two_w);
@@ -645,7 +598,7 @@ int ld_dense_check(const u64* h) {
 
 // exclusive scan of flag[0 .. n] in place, its total (flag[n]) read back
 int ld_scan_count(LdRun& R, int64_t* flag, int64_t n, int64_t* total) {
-  LD_RC(gficf_exclusive_scan_i64(R.ctx, flag, n + 1));
+  GFICF_RC(gficf_exclusive_scan_i64(R.ctx, flag, n + 1));
   GFICF_HIP_CHECK(hipMemcpyAsync(total, flag + n, sizeof(int64_t), hipMemcpyDeviceToHost, R.st()));
   GFICF_HIP_CHECK(hipStreamSynchronize(R.st()));
   return GFICF_OK;
@@ -654,12 +607,12 @@ int ld_scan_count(LdRun& R, int64_t* flag, int64_t n, int64_t* total) {
 // local moving on g from (comm, K, size) until nothing moves
 int ld_local_moving(LdRun& R, const LdG& g, bool big, int level, int seed, int* passes, double* q_out) {
   LdWs& w = R.w;
-  const unsigned gw = ld_blocks(g.n, 4, LD_GRID), gb = ld_blocks(g.n, 1, LD_GRID_BIG);
-  const uint32_t hseed = ld_hash((uint32_t)seed * 0x9E3779B1u + (uint32_t)level * 0x85EBCA77u + 0x165667B1u);
+  const unsigned gw = gficf_grid_capped(g.n, 4, LD_GRID), gb = gficf_grid_capped(g.n, 1, LD_GRID_BIG);
+  const uint32_t hseed = gficf_comm_hash((uint32_t)seed * 0x9E3779B1u + (uint32_t)level * 0x85EBCA77u + 0x165667B1u);
   GFICF_HIP_CHECK(hipMemsetAsync(w.mark, 0, sizeof(int32_t) * (size_t)g.n, R.st()));
   u64 h[LD_S_N];
   double q_prev = 0.0;
-  LD_RC(ld_quality(R, g, w.comm, &q_prev, h));
+  GFICF_RC(ld_quality(R, g, w.comm, &q_prev, h));
   int t = 0;
   *passes = 0;
   for (int pass = 0; pass < LD_MAX_PASSES; ++pass) {
@@ -678,8 +631,8 @@ int ld_local_moving(LdRun& R, const LdG& g, bool big, int level, int seed, int* 
       hipLaunchKernelGGL(k_ld_apply, dim3(gw), dim3(256), 0, R.st(), g, t, w.comm, (const int32_t*)w.next, w.K, w.size, w.mark, w.scal);
     }
     double q = 0.0;
-    LD_RC(ld_quality(R, g, w.comm, &q, h));
-    LD_RC(ld_dense_check(h));
+    GFICF_RC(ld_quality(R, g, w.comm, &q, h));
+    GFICF_RC(ld_dense_check(h));
     if (!(uint32_t)h[LD_S_CHANGED]) break;
     if (q < q_prev) {                                      // a pass that lowers Q is undone and ends the level
       GFICF_HIP_CHECK(hipMemcpyAsync(w.comm, w.snapc, sizeof(int32_t) * (size_t)g.n, hipMemcpyDeviceToDevice, R.st()));
@@ -696,7 +649,7 @@ int ld_local_moving(LdRun& R, const LdG& g, bool big, int level, int seed, int* 
 // the refinement of (comm, K) on g into w.ref (labels: a member of the refined community, whose ref is itself)
 int ld_refine(LdRun& R, const LdG& g, bool big, int64_t* rounds) {
   LdWs& w = R.w;
-  const unsigned gw = ld_blocks(g.n, 4, LD_GRID), gb = ld_blocks(g.n, 1, LD_GRID_BIG), gv = ld_blocks(g.n, 256, 1u << 30);
+  const unsigned gw = gficf_grid_capped(g.n, 4, LD_GRID), gb = gficf_grid_capped(g.n, 1, LD_GRID_BIG), gv = gficf_grid_capped(g.n, 256, 1u << 30);
   hipLaunchKernelGGL(k_rf_init, dim3(gv), dim3(256), 0, R.st(), g.n, g.kv, w.ref, w.rsize, w.Kr);
   hipLaunchKernelGGL(k_rf_ext, dim3(gw), dim3(256), 0, R.st(), g, 1, (const int32_t*)w.comm, (const int32_t*)w.ref, w.ec, w.ext);
   u64 h[LD_S_N];
@@ -710,8 +663,8 @@ int ld_refine(LdRun& R, const LdG& g, bool big, int64_t* rounds) {
       hipLaunchKernelGGL(k_rf_propose<true>, dim3(gb), dim3(256), 0, R.st(), g, R.r, (const int32_t*)w.comm, (const u64*)w.K, (const int32_t*)w.ref,
                          (const int32_t*)w.rsize, (const u64*)w.Kr, (const u64*)w.ext, (const u64*)w.ec, w.prop, w.scal);
     hipLaunchKernelGGL(k_rf_commit, dim3(gv), dim3(256), 0, R.st(), g.n, g.kv, (const int32_t*)w.prop, w.ref, w.rsize, w.Kr, w.scal);
-    LD_RC(ld_read_scal(R, h));
-    LD_RC(ld_dense_check(h));
+    GFICF_RC(ld_read_scal(R, h));
+    GFICF_RC(ld_dense_check(h));
     if (!(uint32_t)h[LD_S_CHANGED]) break;
     GFICF_HIP_CHECK(hipMemsetAsync(w.ext, 0, sizeof(u64) * (size_t)g.n, R.st()));
     hipLaunchKernelGGL(k_rf_ext, dim3(gw), dim3(256), 0, R.st(), g, 0, (const int32_t*)w.comm, (const int32_t*)w.ref, w.ec, w.ext);
@@ -722,53 +675,53 @@ int ld_refine(LdRun& R, const LdG& g, bool big, int64_t* rounds) {
 // one iteration from the canonical labels in w.comm (N entries); the finest vertices' labels come out in w.lab
 int ld_iteration(LdRun& R, int seed) {
   LdWs& w = R.w;
-  const unsigned gN = ld_blocks(R.N, 256, 1u << 30);
-  hipLaunchKernelGGL(k_ld_iota, dim3(gN), dim3(256), 0, R.st(), R.N, w.top);
+  const unsigned gN = gficf_grid_capped(R.N, 256, 1u << 30);
+  hipLaunchKernelGGL(k_comm_iota, dim3(gN), dim3(256), 0, R.st(), R.N, w.top);
   LdG g = R.g0;
   bool big = R.big0;
   const bool debug = getenv("GFICF_LEIDEN_DEBUG") != nullptr;      // per-level trace on stderr
   u64 h[LD_S_N];
   for (int level = 0; level < LD_MAX_LEVELS; ++level) {
-    LD_RC(ld_accum(R, g, w.comm));
+    GFICF_RC(ld_accum(R, g, w.comm));
     int passes = 0;
     int64_t rounds = 0;
     double q_level = 0.0;
-    LD_RC(ld_local_moving(R, g, big, level, seed, &passes, &q_level));
-    const unsigned gv = ld_blocks(g.n + 1, 256, 1u << 30);
+    GFICF_RC(ld_local_moving(R, g, big, level, seed, &passes, &q_level));
+    const unsigned gv = gficf_grid_capped(g.n + 1, 256, 1u << 30);
     int64_t n_comm = 0, n2 = 0;
     hipLaunchKernelGGL(k_ld_flag_size, dim3(gv), dim3(256), 0, R.st(), g.n, (const int32_t*)w.size, w.flag);
-    LD_RC(ld_scan_count(R, w.flag, g.n, &n_comm));
+    GFICF_RC(ld_scan_count(R, w.flag, g.n, &n_comm));
     if (debug) fprintf(stderr, "[leiden] level %d: %lld vertices%s, %d passes of local moving, Q %.9f, %lld communities\n", level, (long long)g.n,
                        big ? " (long rows)" : "", passes, q_level, (long long)n_comm);
     if (n_comm == g.n) break;                              // every community is a single vertex of the level
-    LD_RC(ld_refine(R, g, big, &rounds));
+    GFICF_RC(ld_refine(R, g, big, &rounds));
     hipLaunchKernelGGL(k_ld_flag_ref, dim3(gv), dim3(256), 0, R.st(), g.n, (const int32_t*)w.ref, w.newid);
-    LD_RC(ld_scan_count(R, w.newid, g.n, &n2));
+    GFICF_RC(ld_scan_count(R, w.newid, g.n, &n2));
     if (debug) fprintf(stderr, "[leiden]          %lld refinement rounds, %lld refined communities\n", (long long)rounds, (long long)n2);
     if (n2 == g.n) break;                                  // the refinement merged nothing
     // aggregation by the refined partition
     const LdLevel& L = w.lvl[level & 1];
-    const unsigned gw = ld_blocks(g.n, 4, LD_GRID), gb = ld_blocks(g.n, 1, LD_GRID_BIG), g2 = ld_blocks(n2, 256, 1u << 30);
+    const unsigned gw = gficf_grid_capped(g.n, 4, LD_GRID), gb = gficf_grid_capped(g.n, 1, LD_GRID_BIG), g2 = gficf_grid_capped(n2, 256, 1u << 30);
     GFICF_HIP_CHECK(hipMemsetAsync(L.kv, 0, sizeof(u64) * (size_t)n2, R.st()));
     GFICF_HIP_CHECK(hipMemsetAsync(L.beg, 0, sizeof(int64_t) * (size_t)(n2 + 1), R.st()));
     GFICF_HIP_CHECK(hipMemsetAsync(w.cur, 0, sizeof(u64) * (size_t)n2, R.st()));
     GFICF_HIP_CHECK(hipMemsetAsync(w.scal + LD_S_BIG, 0, sizeof(u64), R.st()));
-    hipLaunchKernelGGL(k_ld_fill32, dim3(ld_blocks(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, INT32_MAX, w.first);
-    hipLaunchKernelGGL(k_ag_vertex, dim3(ld_blocks(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g, (const int32_t*)w.ref, (const int64_t*)w.newid,
+    hipLaunchKernelGGL(k_comm_fill<int32_t>, dim3(gficf_grid_capped(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, INT32_MAX, w.first);
+    hipLaunchKernelGGL(k_ag_vertex, dim3(gficf_grid_capped(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g, (const int32_t*)w.ref, (const int64_t*)w.newid,
                        (const int32_t*)w.comm, L.kv, L.beg, w.first);
-    LD_RC(gficf_exclusive_scan_i64(R.ctx, L.beg, n2 + 1));
+    GFICF_RC(gficf_exclusive_scan_i64(R.ctx, L.beg, n2 + 1));
     hipLaunchKernelGGL(k_ag_emit<false>, dim3(gw), dim3(256), 0, R.st(), g, (const int32_t*)w.ref, (const int64_t*)w.newid, (const int64_t*)L.beg, w.cur,
                        L.nbr, L.wt, w.scal);
     if (big)
       hipLaunchKernelGGL(k_ag_emit<true>, dim3(gb), dim3(256), 0, R.st(), g, (const int32_t*)w.ref, (const int64_t*)w.newid, (const int64_t*)L.beg, w.cur,
                          L.nbr, L.wt, w.scal);
     hipLaunchKernelGGL(k_ag_finish, dim3(g2), dim3(256), 0, R.st(), n2, (const int64_t*)L.beg, (const u64*)w.cur, L.end, w.scal);
-    hipLaunchKernelGGL(k_ag_comm, dim3(ld_blocks(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, (const int32_t*)w.ref, (const int64_t*)w.newid,
+    hipLaunchKernelGGL(k_ag_comm, dim3(gficf_grid_capped(g.n, 256, 1u << 30)), dim3(256), 0, R.st(), g.n, (const int32_t*)w.ref, (const int64_t*)w.newid,
                        (const int32_t*)w.comm, (const int32_t*)w.first, w.comm2);
     hipLaunchKernelGGL(k_ag_top, dim3(gN), dim3(256), 0, R.st(), R.N, w.top, (const int32_t*)w.ref, (const int64_t*)w.newid);
     GFICF_HIP_CHECK(hipMemcpyAsync(w.comm, w.comm2, sizeof(int32_t) * (size_t)n2, hipMemcpyDeviceToDevice, R.st()));
-    LD_RC(ld_read_scal(R, h));
-    LD_RC(ld_dense_check(h));
+    GFICF_RC(ld_read_scal(R, h));
+    GFICF_RC(ld_dense_check(h));
     big = (uint32_t)h[LD_S_BIG] != 0;
     g = LdG{n2, L.beg, L.end, L.nbr, L.wt, L.kv};
   }
@@ -799,7 +752,7 @@ int gficf_leiden_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indptr, cons
                         int n_iterations, int seed, const int32_t* d_init_or_null, int32_t* d_labels, int64_t* n_clusters, double* modularity, void* d_ws,
                         size_t ws_bytes) {
   GFICF_CTX_ENTER(ctx);
-  LD_RC(ld_check_args(N, nnz, resolution));
+  GFICF_RC(ld_check_args(N, nnz, resolution));
   if (n_iterations < 1) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_iterations = %d: must be at least 1", n_iterations);
   if (!n_clusters) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_clusters is NULL");
   *n_clusters = 0;
@@ -814,32 +767,29 @@ int gficf_leiden_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indptr, cons
   LdWs& w = R.w;
   hipStream_t st = ctx->stream;
   bool no_edges = false;
-  LD_RC(ld_setup(R, d_indptr, d_indices, d_x, d_init_or_null, &no_edges));
-  const unsigned gN = ld_blocks(N, 256, 1u << 30);
+  GFICF_RC(ld_setup(R, d_indptr, d_indices, d_x, d_init_or_null, &no_edges));
+  const unsigned gN = gficf_grid_capped(N, 256, 1u << 30);
   if (no_edges) {                                          // every vertex is its own cluster, Q = 0
-    hipLaunchKernelGGL(k_ld_iota, dim3(gN), dim3(256), 0, st, N, d_labels);
+    hipLaunchKernelGGL(k_comm_iota, dim3(gN), dim3(256), 0, st, N, d_labels);
     GFICF_HIP_CHECK(hipStreamSynchronize(st));
     *n_clusters = N;
     return GFICF_OK;
   }
   if (d_init_or_null) ld_canon(R, d_init_or_null, w.comm);
-  else hipLaunchKernelGGL(k_ld_iota, dim3(gN), dim3(256), 0, st, N, w.comm);
+  else hipLaunchKernelGGL(k_comm_iota, dim3(gN), dim3(256), 0, st, N, w.comm);
   for (int it = 0; it < n_iterations; ++it) {
-    LD_RC(ld_iteration(R, seed));
+    GFICF_RC(ld_iteration(R, seed));
     ld_canon(R, w.lab, w.comm);                            // the next iteration's start, and the spelling the result is numbered from
   }
   // Q of the result, its clusters by decreasing size (ties: the smaller canonical label = the first vertex)
   u64 h[LD_S_N];
   double q = 0.0;
-  LD_RC(ld_accum(R, R.g0, w.comm));
-  LD_RC(ld_quality(R, R.g0, w.comm, &q, h));
+  GFICF_RC(ld_accum(R, R.g0, w.comm));
+  GFICF_RC(ld_quality(R, R.g0, w.comm, &q, h));
   int64_t nc = 0;
-  hipLaunchKernelGGL(k_ld_flag_size, dim3(ld_blocks(N + 1, 256, 1u << 30)), dim3(256), 0, st, N, (const int32_t*)w.size, w.flag);
-  LD_RC(ld_scan_count(R, w.flag, N, &nc));
-  hipLaunchKernelGGL(k_ld_size_keys, dim3(gN), dim3(256), 0, st, N, (const int32_t*)w.size, w.skv[0]);
-  LD_RC(gficf_radix_sort_kv(ctx, w.skv[0], w.skv[1], w.shist, N, gficf_bit_width(N), w.skey, w.sid));
-  hipLaunchKernelGGL(k_ld_rank, dim3(gN), dim3(256), 0, st, N, (const uint32_t*)w.sid, w.rank);
-  hipLaunchKernelGGL(k_ld_final, dim3(gN), dim3(256), 0, st, N, (const int32_t*)w.comm, (const int32_t*)w.rank, d_labels);
+  hipLaunchKernelGGL(k_ld_flag_size, dim3(gficf_grid_capped(N + 1, 256, 1u << 30)), dim3(256), 0, st, N, (const int32_t*)w.size, w.flag);
+  GFICF_RC(ld_scan_count(R, w.flag, N, &nc));
+  GFICF_RC(gficf_comm_number_by_size(ctx, N, N, w.size, w.comm, w.sort, w.rank, d_labels));      // every label in [0, N): the unused ones sort last
   GFICF_HIP_CHECK(hipStreamSynchronize(st));
   GFICF_HIP_CHECK(hipGetLastError());
   *n_clusters = nc;
@@ -850,7 +800,7 @@ int gficf_leiden_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indptr, cons
 int gficf_leiden_refine_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indptr, const int32_t* d_indices, const double* d_x, int64_t nnz,
                                double resolution, const int32_t* d_labels_in, int32_t* d_refined_out, int64_t* n_refined, void* d_ws, size_t ws_bytes) {
   GFICF_CTX_ENTER(ctx);
-  LD_RC(ld_check_args(N, nnz, resolution));
+  GFICF_RC(ld_check_args(N, nnz, resolution));
   if (!n_refined) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_refined is NULL");
   *n_refined = 0;
   if (N == 0) return GFICF_OK;
@@ -862,21 +812,21 @@ int gficf_leiden_refine_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indpt
   ld_carve(&R.w, d_ws, N, nnz);
   LdWs& w = R.w;
   bool no_edges = false;
-  LD_RC(ld_setup(R, d_indptr, d_indices, d_x, d_labels_in, &no_edges));
-  const unsigned gN = ld_blocks(N, 256, 1u << 30);
+  GFICF_RC(ld_setup(R, d_indptr, d_indices, d_x, d_labels_in, &no_edges));
+  const unsigned gN = gficf_grid_capped(N, 256, 1u << 30);
   if (no_edges) {
-    hipLaunchKernelGGL(k_ld_iota, dim3(gN), dim3(256), 0, ctx->stream, N, d_refined_out);
+    hipLaunchKernelGGL(k_comm_iota, dim3(gN), dim3(256), 0, ctx->stream, N, d_refined_out);
     GFICF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *n_refined = N;
     return GFICF_OK;
   }
   GFICF_HIP_CHECK(hipMemcpyAsync(w.comm, d_labels_in, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
-  LD_RC(ld_accum(R, R.g0, w.comm));
+  GFICF_RC(ld_accum(R, R.g0, w.comm));
   int64_t rounds = 0;
-  LD_RC(ld_refine(R, R.g0, R.big0, &rounds));
+  GFICF_RC(ld_refine(R, R.g0, R.big0, &rounds));
   int64_t n2 = 0;
-  hipLaunchKernelGGL(k_ld_flag_ref, dim3(ld_blocks(N + 1, 256, 1u << 30)), dim3(256), 0, ctx->stream, N, (const int32_t*)w.ref, w.newid);
-  LD_RC(ld_scan_count(R, w.newid, N, &n2));
+  hipLaunchKernelGGL(k_ld_flag_ref, dim3(gficf_grid_capped(N + 1, 256, 1u << 30)), dim3(256), 0, ctx->stream, N, (const int32_t*)w.ref, w.newid);
+  GFICF_RC(ld_scan_count(R, w.newid, N, &n2));
   ld_canon(R, w.ref, d_refined_out);                       // one spelling: the smallest member
   GFICF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   GFICF_HIP_CHECK(hipGetLastError());
@@ -887,7 +837,7 @@ int gficf_leiden_refine_device(gficf_ctx* ctx, int64_t N, const int64_t* d_indpt
 int gficf_leiden_host(gficf_ctx* ctx, int64_t N, const int64_t* indptr, const int32_t* indices, const double* x, int64_t nnz, double resolution,
                       int n_iterations, int seed, const int32_t* init_or_null, int32_t* labels, int64_t* n_clusters, double* modularity) {
   GFICF_CTX_ENTER(ctx);
-  LD_RC(ld_check_args(N, nnz, resolution));
+  GFICF_RC(ld_check_args(N, nnz, resolution));
   if (n_iterations < 1) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_iterations = %d: must be at least 1", n_iterations);
   if (!n_clusters) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_clusters is NULL");
   *n_clusters = 0;
@@ -896,7 +846,7 @@ int gficf_leiden_host(gficf_ctx* ctx, int64_t N, const int64_t* indptr, const in
   if (!indptr || !labels || (nnz > 0 && (!indices || !x))) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   std::vector<int64_t> ptr;
   int64_t m = 0;
-  LD_RC(gficf_host_colptr(indptr, 1, N, "indptr", ptr, &m));
+  GFICF_RC(gficf_host_colptr(indptr, 1, N, "indptr", ptr, &m));
   if (m != nnz) GFICF_FAIL(GFICF_ERR_BAD_CSC, "indptr[N] = %lld, nnz = %lld", (long long)m, (long long)nnz);
   const size_t ws_b = gficf_leiden_workspace_bytes(N, nnz), e = (size_t)(nnz > 0 ? nnz : 1);
   gficf_host_io io{ctx, "gficf_leiden_host"};
@@ -922,14 +872,14 @@ int gficf_leiden_host(gficf_ctx* ctx, int64_t N, const int64_t* indptr, const in
 int gficf_leiden_refine_host(gficf_ctx* ctx, int64_t N, const int64_t* indptr, const int32_t* indices, const double* x, int64_t nnz, double resolution,
                              const int32_t* labels_in, int32_t* refined_out, int64_t* n_refined) {
   GFICF_CTX_ENTER(ctx);
-  LD_RC(ld_check_args(N, nnz, resolution));
+  GFICF_RC(ld_check_args(N, nnz, resolution));
   if (!n_refined) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "n_refined is NULL");
   *n_refined = 0;
   if (N == 0) return GFICF_OK;
   if (!indptr || !labels_in || !refined_out || (nnz > 0 && (!indices || !x))) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   std::vector<int64_t> ptr;
   int64_t m = 0;
-  LD_RC(gficf_host_colptr(indptr, 1, N, "indptr", ptr, &m));
+  GFICF_RC(gficf_host_colptr(indptr, 1, N, "indptr", ptr, &m));
   if (m != nnz) GFICF_FAIL(GFICF_ERR_BAD_CSC, "indptr[N] = %lld, nnz = %lld", (long long)m, (long long)nnz);
   const size_t ws_b = gficf_leiden_refine_workspace_bytes(N, nnz), e = (size_t)(nnz > 0 ? nnz : 1);
   gficf_host_io io{ctx, "gficf_leiden_refine_host"};

@@ -1,9 +1,10 @@
 // prim_probe.hip — test infrastructure: C entries onto the internal primitives of libgficf_hip.so (common.h), which its C ABI
-// does not export, and onto the header-only code the add-ons share (block_ops.h, addon_sort.h).  Built and loaded by
-// tests/helpers/prim_probe.py; never part of the product.
+// does not export, and onto the header-only code the add-ons share (block_ops.h, addon_sort.h) and louvain.hip shares with
+// leiden.hip (community_ops.h).  Built and loaded by tests/helpers/prim_probe.py; never part of the product.
 #include "addon_sort.h"
 #include "block_ops.h"
 #include "common.h"
+#include "community_ops.h"
 
 namespace {
 
@@ -35,6 +36,29 @@ __global__ __launch_bounds__(256) void k_probe_lds_sort(gficf_u64* __restrict__ 
 template <typename T, typename I>
 __global__ __launch_bounds__(256) void k_probe_lower(const T* __restrict__ a, I n, const T* __restrict__ q, int64_t m, I* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) out[i] = gficf_lower_bound(a, n, q[i]);
+}
+
+// One wave and a table of 256 slots with 64 guard entries behind it.  Round r: lane l brings community c[64 r + l] (negative:
+// the lane sits the round out) with weight w[64 r + l]; slot / own = what gficf_comm_insert reported.  The table and its guard
+// are copied out at the end (320 entries each).
+constexpr int PROBE_SLOTS = 256, PROBE_GUARD = 64;
+__global__ __launch_bounds__(64) void k_probe_insert(int rounds, const int32_t* __restrict__ c, const gficf_u64* __restrict__ w, int32_t* __restrict__ slot,
+                                                     int32_t* __restrict__ own, int32_t* __restrict__ key_out, gficf_u64* __restrict__ val_out) {
+  __shared__ int32_t key[PROBE_SLOTS + PROBE_GUARD];
+  __shared__ gficf_u64 val[PROBE_SLOTS + PROBE_GUARD];
+  const int lane = threadIdx.x;
+  for (int t = lane; t < PROBE_SLOTS + PROBE_GUARD; t += 64) { key[t] = t < PROBE_SLOTS ? -1 : 0x5A5A5A5A; val[t] = t < PROBE_SLOTS ? 0ull : 0x5A5A5A5A5A5A5A5Aull; }
+  GFICF_WAVE_SYNC();
+  for (int r = 0; r < rounds; ++r) {
+    const int i = r * 64 + lane;
+    if (c[i] >= 0) {
+      bool o = false;
+      slot[i] = gficf_comm_insert<PROBE_SLOTS>(key, val, c[i], w[i], &o);
+      own[i] = o ? 1 : 0;
+    }
+    GFICF_WAVE_SYNC();
+  }
+  for (int t = lane; t < PROBE_SLOTS + PROBE_GUARD; t += 64) { key_out[t] = key[t]; val_out[t] = val[t]; }
 }
 
 }  // namespace
@@ -101,5 +125,36 @@ int probe_lower_bound_u32(void* ctx, const uint32_t* a, int n, const uint32_t* q
   GFICF_HIP_CHECK(hipGetLastError());
   return GFICF_OK;
 }
+
+// The numbering by decreasing size of community_ops.h through buffers carved as louvain.hip and leiden.hip carve them.
+// ws == NULL: only *total (the block to allocate) is written.  Otherwise offs[0 .. 5) = the byte offsets of kv[0], kv[1], key,
+// id, hist in ws, and the numbering of the labels [0, C) of N vertices is enqueued.
+int probe_comm_number(void* ctx, void* ws, int64_t C, int64_t N, const int32_t* cnt, const int32_t* lab, int32_t* rank, int32_t* out, int64_t* offs,
+                      int64_t* total) {
+  gficf_carver cv;
+  cv.base = (char*)ws;
+  gficf_comm_sort_bufs s;
+  s.take(cv, (size_t)(N > 0 ? N : 1), N);
+  *total = (int64_t)cv.total();
+  if (!ws) return GFICF_OK;
+  const void* p[5] = {s.kv[0], s.kv[1], s.key, s.id, s.hist};
+  for (int i = 0; i < 5; ++i) offs[i] = (int64_t)((const char*)p[i] - (const char*)ws);
+  const int rc = gficf_comm_number_by_size((gficf_ctx*)ctx, C, N, cnt, lab, s, rank, out);
+  if (rc) return rc;
+  GFICF_HIP_CHECK(hipGetLastError());
+  return GFICF_OK;
+}
+
+// `rounds` rounds of 64 inserts by one wave into one 256-slot table (k_probe_insert)
+int probe_comm_insert(void* ctx, int rounds, const int32_t* c, const unsigned long long* w, int32_t* slot, int32_t* own, int32_t* key_out,
+                      unsigned long long* val_out) {
+  hipLaunchKernelGGL(k_probe_insert, dim3(1), dim3(64), 0, ((gficf_ctx*)ctx)->stream, rounds, c, w, slot, own, key_out, val_out);
+  GFICF_HIP_CHECK(hipGetLastError());
+  return GFICF_OK;
+}
+
+unsigned probe_grid_capped(int64_t n, int64_t per, unsigned cap) { return gficf_grid_capped(n, per, cap); }
+
+unsigned probe_grid_1d(int64_t n) { return gficf_grid_1d(n); }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 """Builds tests/helpers/prim_probe.hip against gficf_amd/csrc/common.h into tests/helpers/libprim_probe.so (linked to
 libgficf_hip.so) and binds it with ctypes: the radix sort, the int64 exclusive scan and the scan epoch of a context, which
 the library keeps internal (the exported gficf_* surface is pinned by tests/test_abi.py), and the header-only code the add-ons
-share (block_ops.h, addon_sort.h): the grouped f64 sort, the block sum and max, the LDS sort and the lower bound.  Test
+share (block_ops.h, addon_sort.h): the grouped f64 sort, the block sum and max, the LDS sort, the lower bound and the capped
+grid; and what louvain.hip and leiden.hip share (community_ops.h): the numbering by size and the table insert.  Test
 infrastructure only."""
 from __future__ import annotations
 
@@ -17,11 +18,12 @@ SO = os.path.join(HERE, "libprim_probe.so")
 LIBDIR = os.path.join(ROOT, "gficf_amd")
 CSRC = os.path.join(LIBDIR, "csrc")
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "block_ops.h"), os.path.join(CSRC, "addon_sort.h"),
-           os.path.join(ROOT, "include", "gficf_hip.h")]
+           os.path.join(CSRC, "community_ops.h"), os.path.join(ROOT, "include", "gficf_hip.h")]
 
 SYMBOLS = ["probe_radix_sort_kv", "probe_radix_sort_hist_len", "probe_exclusive_scan_i64", "probe_get_scan_epoch",
            "probe_set_scan_epoch", "probe_ctx_sync", "probe_sort_f64", "probe_block_ops", "probe_lds_sort_u64",
-           "probe_lower_bound_f64", "probe_lower_bound_u32"]
+           "probe_lower_bound_f64", "probe_lower_bound_u32", "probe_comm_number", "probe_comm_insert", "probe_grid_capped",
+           "probe_grid_1d"]
 
 
 def hipcc() -> str | None:
@@ -72,6 +74,10 @@ class Probe:
             ("probe_lds_sort_u64", ci, [vp, vp, ci, i64]),
             ("probe_lower_bound_f64", ci, [vp, vp, i64, vp, i64, vp]),
             ("probe_lower_bound_u32", ci, [vp, vp, ci, vp, i64, vp]),
+            ("probe_comm_number", ci, [vp, vp, i64, i64, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+            ("probe_comm_insert", ci, [vp, ci, vp, vp, vp, vp, vp, vp]),
+            ("probe_grid_capped", ctypes.c_uint, [i64, i64, ctypes.c_uint]),
+            ("probe_grid_1d", ctypes.c_uint, [i64]),
         ]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
@@ -118,3 +124,24 @@ class Probe:
 
     def lower_u32(self, ctx, a, n, q, m, out) -> int:
         return self.L.probe_lower_bound_u32(ctx, a, int(n), q, int(m), out)
+
+    def comm_number_bytes(self, N) -> int:
+        """The block gficf_comm_sort_bufs::take asks for, for N vertices."""
+        total = ctypes.c_int64(0)
+        assert self.L.probe_comm_number(None, None, 0, int(N), None, None, None, None, None, ctypes.byref(total)) == 0
+        return total.value
+
+    def comm_number(self, ctx, ws, C, N, cnt, lab, rank, out):
+        """Enqueues the numbering; returns (rc, the byte offsets of kv[0], kv[1], key, id, hist in ws)."""
+        offs, total = (ctypes.c_int64 * 5)(), ctypes.c_int64(0)
+        rc = self.L.probe_comm_number(ctx, ws, int(C), int(N), cnt, lab, rank, out, offs, ctypes.byref(total))
+        return rc, list(offs)
+
+    def comm_insert(self, ctx, rounds, c, w, slot, own, key_out, val_out) -> int:
+        return self.L.probe_comm_insert(ctx, int(rounds), c, w, slot, own, key_out, val_out)
+
+    def grid_capped(self, n, per, cap) -> int:
+        return int(self.L.probe_grid_capped(int(n), int(per), int(cap)))
+
+    def grid_1d(self, n) -> int:
+        return int(self.L.probe_grid_1d(int(n)))

@@ -11,6 +11,9 @@
                form of its first pass (descending, mask, status, count) and of its groups (none, array, divisor), the
                buffers carved by gficf_sort_bufs::take, nothing written outside them
   block ops    block_ops.h: the folded sum and max against the same tree in NumPy, bit for bit; the LDS sort; the lower bound
+               and the capped grid
+  communities  community_ops.h: the numbering of labels by decreasing size against a NumPy stable sort by (-size, id), and the
+               LDS table insert of one wave (owners, exact sums, a full table)
 
 The sort, the scan and the add-ons' headers are reached through tests/helpers/prim_probe.py; references are exact (NumPy /
 torch stable sorts, integer cumulative sums, the same float64 additions in the same order)."""
@@ -508,3 +511,116 @@ def test_lower_bound(probe, ctx, n):
         assert lower(ctx, _ptr(d_a), n, _ptr(d_q), len(q), _ptr(out)) == OK and probe.sync(ctx) == OK
         assert np.array_equal(out[:len(q)].cpu().numpy(), np.searchsorted(a, q, side="left"))
         assert bool((out[len(q):] == -7).all())
+
+
+def test_grid_capped_on_the_host(probe):
+    """n = 0, 1, per, per + 1 and beyond the cap; gficf_grid_1d is the same helper at 256 a workgroup, capped at 16384."""
+    for per, cap in ((256, 16384), (4, 1536), (2, 1280), (1, 1280), (256, 1 << 30)):
+        want = [1, 1, 1, 2, cap]
+        got = [probe.grid_capped(n, per, cap) for n in (0, 1, per, per + 1, per * cap + 1)]
+        assert got == want, (per, cap, got)
+        assert probe.grid_capped(per * cap, per, cap) == cap and probe.grid_capped(per * (cap - 1) + 1, per, cap) == cap
+    for n in (0, 1, 256, 257, 256 * 16384 + 1):
+        assert probe.grid_1d(n) == probe.grid_capped(n, 256, 16384)
+
+
+# ------------------------------------------------------------------------------------------------ what Louvain and Leiden share
+def _number_cases():
+    rng = np.random.default_rng(5)
+    sizes = np.zeros(257, dtype=np.int64)                   # a second workgroup of the C-sized kernels; unused labels (size 0)
+    used = rng.choice(257, 180, replace=False)
+    sizes[used] = 1
+    np.add.at(sizes, rng.choice(used, 600 - 180), 1)        # many ties
+    return {"C1": (np.array([7]), None), "C5_two_ties": (np.array([3, 5, 3, 1, 5]), None), "C257_N600_zeros": (sizes, None),
+            "C300_singletons": (np.ones(300, dtype=np.int64), rng.permutation(300))}
+
+
+NUMBER_CASES = _number_cases()
+
+
+@pytest.mark.parametrize("case", sorted(NUMBER_CASES))
+def test_number_by_size_against_stable_sort(probe, ctx, case):
+    """rank = the position of a label in the stable sort by (-size, id) — a label nobody carries comes last, as Leiden's
+    unused ones do — and out[v] = rank[lab[v]]; nothing written behind rank, out or outside the sort's buffers."""
+    sizes, lab = NUMBER_CASES[case]
+    C, N = len(sizes), int(sizes.sum())
+    if lab is None:
+        lab = np.random.default_rng(C).permutation(np.repeat(np.arange(C), sizes))
+    assert len(lab) == N and np.array_equal(np.bincount(lab, minlength=C), sizes)
+    order = np.lexsort((np.arange(C), -sizes))
+    want_rank = np.empty(C, dtype=np.int64)
+    want_rank[order] = np.arange(C)
+    total = probe.comm_number_bytes(N)
+    ws = torch.full((total,), 0x5A, dtype=torch.uint8, device=DEV)
+    d_cnt, d_lab = _dev(sizes.astype(np.int32)), _dev(lab.astype(np.int32))
+    rank, out = _padded(C, CANARY, torch.int32), _padded(N, CANARY, torch.int32)
+    torch.cuda.synchronize()
+    rc, offs = probe.comm_number(ctx, _ptr(ws), C, N, _ptr(d_cnt), _ptr(d_lab), _ptr(rank), _ptr(out))
+    assert rc == OK and probe.sync(ctx) == OK
+    assert np.array_equal(rank[:C].cpu().numpy(), want_rank), case
+    assert np.array_equal(out[:N].cpu().numpy(), want_rank[lab]), case
+    assert bool((rank[C:] == CANARY).all()) and bool((out[N:] == CANARY).all())
+    assert np.array_equal(d_cnt.cpu().numpy(), sizes) and np.array_equal(d_lab.cpu().numpy(), lab)      # the inputs are left alone
+    used = torch.zeros(total, dtype=torch.bool, device=DEV)
+    for off, size in zip(offs, (8 * N, 8 * N, 4 * N, 4 * N, 8 * probe.hist_len(N, _bit_width(N)))):
+        assert off % 256 == 0 and off + size <= total
+        used[off:off + size] = True
+    assert bool((ws[~used] == 0x5A).all()), case
+
+
+def _insert(probe, ctx, c, w):
+    """c, w: (rounds, 64) communities (negative: the lane sits out) and weights -> slot, own (rounds, 64; -7 where the lane sat
+    out), and the table's 256 keys and sums; the 64 guard entries behind the table must be untouched."""
+    rounds = c.shape[0]
+    d_c, d_w = _dev(c.astype(np.int32).reshape(-1)), _dev(w.astype(np.uint64).view(np.int64).reshape(-1))
+    slot, own = (torch.full((rounds * 64 + 16,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+    key, val = _padded(320, CANARY, torch.int32), _padded(320, CANARY, torch.int64)
+    torch.cuda.synchronize()
+    assert probe.comm_insert(ctx, rounds, _ptr(d_c), _ptr(d_w), _ptr(slot), _ptr(own), _ptr(key), _ptr(val)) == OK and probe.sync(ctx) == OK
+    assert bool((slot[rounds * 64:] == -7).all()) and bool((own[rounds * 64:] == -7).all())
+    assert bool((key[256:320] == 0x5A5A5A5A).all()) and bool((val[256:320] == 0x5A5A5A5A5A5A5A5A).all())      # the guard behind the table
+    assert bool((key[320:] == CANARY).all()) and bool((val[320:] == CANARY).all())
+    return (slot[:rounds * 64].cpu().numpy().reshape(rounds, 64), own[:rounds * 64].cpu().numpy().reshape(rounds, 64), key[:256].cpu().numpy(),
+            val[:256].cpu().numpy().view(np.uint64))
+
+
+def _check_table(c, w, slot, own, key, val, full=()):
+    """Every insert that found room: its slot holds its community, one owner per community, the slot's sum is the total of
+    the lanes that brought it; the slots nobody claimed are empty."""
+    refused = np.isin(c, np.array(full, dtype=np.int64))
+    there = (c >= 0) & ~refused
+    assert (slot[there] >= 0).all() and (slot[there] < 256).all() and (slot[refused] == -1).all() and (own[refused] == 0).all()
+    assert np.array_equal(key[slot[there]], c[there])
+    for comm in np.unique(c[there]):
+        m = there & (c == comm)
+        assert len(np.unique(slot[m])) == 1 and own[m].sum() == 1
+        assert val[slot[m][0]] == np.add.reduce(w[m], dtype=np.uint64)
+    free = np.setdiff1d(np.arange(256), slot[there])
+    assert (key[free] == -1).all() and (val[free] == 0).all()
+
+
+def test_table_insert_of_one_wave(probe, ctx):
+    rng = np.random.default_rng(3)
+    # 64 distinct communities: every lane owns its slot, the sums are the weights themselves (beyond 2^53: exact integers)
+    c = rng.choice(2 ** 31 - 1, 64, replace=False).reshape(1, 64)
+    w = rng.integers(1, 2 ** 62, (1, 64), dtype=np.uint64)
+    slot, own, key, val = _insert(probe, ctx, c, w)
+    assert (own == 1).all() and len(np.unique(slot)) == 64
+    _check_table(c, w, slot, own, key, val)
+    # 64 lanes on 3 communities: one owner each, every sum the total of its lanes
+    c3 = rng.choice(np.array([5, 261, 1_000_000_007]), 64).reshape(1, 64)
+    assert len(np.unique(c3)) == 3
+    w3 = rng.integers(1, 2 ** 56, (1, 64), dtype=np.uint64)
+    slot, own, key, val = _insert(probe, ctx, c3, w3)
+    assert own.sum() == 3
+    _check_table(c3, w3, slot, own, key, val)
+    # 257 distinct communities over five rounds (64, 64, 64, 64, 1): the table is full when the last one comes — it alone gets
+    # -1, owns nothing, and nothing is written past the table
+    c5 = np.full(320, -1, dtype=np.int64)
+    c5[:257] = rng.choice(2 ** 31 - 1, 257, replace=False)
+    w5 = rng.integers(1, 2 ** 40, 320, dtype=np.uint64)
+    c5, w5 = c5.reshape(5, 64), w5.reshape(5, 64)
+    slot, own, key, val = _insert(probe, ctx, c5, w5)
+    assert (slot[c5 >= 0] == -1).sum() == 1 and slot[4, 0] == -1 and (slot[c5 < 0] == -7).all()
+    assert own[c5 >= 0].sum() == 256 and len(np.unique(slot[:4])) == 256
+    _check_table(c5, w5, slot, own, key, val, full=(c5[4, 0],))
