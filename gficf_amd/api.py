@@ -1047,7 +1047,7 @@ def gmt_pathways(gmt_file, convertToEns: bool = False, convertHu2Mm: bool = Fals
 
 
 def gsea(stats, pathways_ptr, pathways_rows, nsim: int = 1000, min_size=1, max_size=np.inf, seed: int = 180582, ret_null: bool = False,
-         ctx: Context | None = None) -> dict:
+         ctx: Context | None = None, *, exact: bool = False) -> dict:
     """Gene-set enrichment of every column of ``stats`` (G x C, one ranking statistic per gene and cluster) for P pathways in
     CSR form (``pathways_ptr``: P + 1 offsets, ``pathways_rows``: rows of ``stats``), fgsea at ``gseaParam = 0`` under the
     relaxed contract of include/gficf_gsea.h: ES and NES are fgsea's, the p-value is ``fgseaSimple``'s estimator over ``nsim``
@@ -1055,6 +1055,15 @@ def gsea(stats, pathways_ptr, pathways_rows, nsim: int = 1000, min_size=1, max_s
 
     Returns ``es``, ``nes``, ``pval`` (P x C; zeros where a pathway is not tested), ``size`` (P), ``tested`` (P; size within
     ``[min_size, min(max_size, G - 1)]``) and, with ``ret_null``, ``sizes`` (the D distinct tested sizes) and ``null`` (D x nsim).
+
+    ``exact=True`` (off by default: the sweep costs far more than the sampled call) adds two P x C outputs that have no
+    permutation floor (include/gficf_gsea_exact.h; the others keep their bits).  ``ptail``: the exact one-sided tail of ES under
+    the uniform null of the set's size, :func:`gsea_tail`; 0 where a pathway is not tested, 1 where ES is 0.  ``pval_exact =
+    min(1, ptail * (nsim + 1) / (n0 + 1))`` with ``n0`` the number of null values of that size that are ``>= 0`` when ES > 0 and
+    ``<= 0`` when ES < 0 (counted on the host in the null table the call makes anyway), and 1 when ES is 0: the exact one-sided
+    tail divided by a sampled probability of the sign.  It is at least the limit of the simple estimator's numerator
+    ``P(ES >= x)``; the two differ by ``P(maxP >= x, -minP >= maxP)``, negligible once p is small.  A set larger than
+    ``GFICF_GSEA_EXACT_MAX_SIZE`` has a NaN ``ptail`` and keeps ``pval`` as its ``pval_exact`` (one warning).
     """
     from . import _gsea_lib
 
@@ -1077,14 +1086,64 @@ def gsea(stats, pathways_ptr, pathways_rows, nsim: int = 1000, min_size=1, max_s
     tested = (size >= lo) & (size <= hi)
     sizes = np.unique(size[tested])
     es, nes, pval = (np.zeros((C, P), dtype=np.float64) for _ in range(3))
-    null = np.zeros((len(sizes), nsim), dtype=np.float64) if ret_null else None
+    null = np.zeros((len(sizes), nsim), dtype=np.float64) if ret_null or exact else None
     ctx = ctx or default_context()
     check(_gsea_lib.load().gficf_gsea_host(ctx.handle, G, C, _np_ptr(S), P, _np_ptr(ptr), _np_ptr(rows), nsim, int(seed) & 0xFFFFFFFF, lo, hi,
-                                           _np_ptr(es), _np_ptr(nes), _np_ptr(pval), _np_ptr(null) if ret_null else None, len(sizes)))
+                                           _np_ptr(es), _np_ptr(nes), _np_ptr(pval), _np_ptr(null) if null is not None else None, len(sizes)))
     out = {"es": es.T, "nes": nes.T, "pval": pval.T, "size": size, "tested": tested}
     if ret_null:
         out["sizes"], out["null"] = sizes, null
+    if exact:
+        out["ptail"], out["pval_exact"] = _gsea_exact_pvalues(G, size, tested, sizes, null, out["es"], out["pval"], nsim, ctx)
     return out
+
+
+def gsea_tail(G: int, size, es, ctx: Context | None = None) -> np.ndarray:
+    """The exact one-sided tail of enrichment scores at ``gseaParam = 0`` (include/gficf_gsea_exact.h): for every pair of a set
+    size ``m`` in ``[1, G - 1]`` and a score ``x`` as :func:`gsea` returns it, the share of the m-subsets of G positions with
+    ``maxP >= x`` (x > 0) or ``minP <= x`` (x < 0); 1 for x == 0.  A lattice-path count in f64, relative error at most
+    ``4 G 2^-52`` down to 1e-290; NaN for a size above ``GFICF_GSEA_EXACT_MAX_SIZE``.  ``size`` and ``es`` broadcast against each
+    other; the result has their shape."""
+    from . import _gsea_exact_lib
+
+    size, es = np.broadcast_arrays(np.asarray(size), np.asarray(es, dtype=np.float64))
+    if size.size and (size.dtype.kind not in "iu" or np.abs(size).max() > np.iinfo(np.int32).max):
+        raise ValueError("size must hold int32 set sizes")
+    if int(G) < 2:
+        raise ValueError("G must be at least 2")
+    shape = size.shape
+    m = np.ascontiguousarray(size, dtype=np.int32).ravel()
+    x = np.ascontiguousarray(es, dtype=np.float64).ravel()
+    tail = np.zeros(len(m), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_gsea_exact_lib.load().gficf_gsea_tail_host(ctx.handle, int(G), len(m), _np_ptr(m), _np_ptr(x), _np_ptr(tail)))
+    return tail.reshape(shape)
+
+
+def _gsea_exact_pvalues(G, size, tested, sizes, null, es, pval, nsim, ctx):
+    """``ptail`` and ``pval_exact`` of :func:`gsea` (P x C) from its ES, its null table and its simple p-values."""
+    from . import _gsea_exact_lib
+
+    t = np.flatnonzero(tested)
+    ptail, pexact = np.zeros_like(es), np.zeros_like(es)
+    if len(t) == 0:
+        return ptail, pexact
+    e = es[t]
+    ptail[t] = gsea_tail(G, size[t][:, None], e, ctx)
+    d = np.searchsorted(sizes, size[t])
+    n_ge, n_le = (null >= 0).sum(axis=1)[d], (null <= 0).sum(axis=1)[d]
+    n0 = np.where(e > 0, n_ge[:, None], n_le[:, None]).astype(np.float64)
+    pe = np.minimum(1.0, ptail[t] * np.float64(nsim + 1) / (n0 + 1.0))
+    pe[e == 0] = 1.0
+    over = np.isnan(ptail[t])
+    if over.any():
+        import warnings
+
+        warnings.warn(f"{int(over.any(axis=1).sum())} pathways hold more than GFICF_GSEA_EXACT_MAX_SIZE = {_gsea_exact_lib.MAX_SIZE} genes: their "
+                      "pval_exact is the simple estimator's pval")
+        pe[over] = pval[t][over]
+    pexact[t] = pe
+    return ptail, pexact
 
 
 def _pathway_csr(pathways: dict, gene_names):
@@ -1100,10 +1159,12 @@ def _pathway_csr(pathways: dict, gene_names):
     return np.asarray(ptr, dtype=np.int64), np.asarray(rows, dtype=np.int32)
 
 
-def fgsea(pathways: dict, stats, nsim: int = 1000, minSize=1, maxSize=np.inf, seed: int = 180582, names=None, ctx: Context | None = None):
+def fgsea(pathways: dict, stats, nsim: int = 1000, minSize=1, maxSize=np.inf, seed: int = 180582, names=None, ctx: Context | None = None, *,
+          exact: bool = False):
     """``fgsea(pathways, stats, minSize, maxSize, gseaParam = 0)`` for one ranked vector: ``stats`` is a ``pandas.Series`` indexed
     by gene name, or an array plus ``names``.  Returns a ``pandas.DataFrame`` ``pathway, pval, padj, ES, NES, size`` of the tested
-    pathways in input order; ``padj = p.adjust(pval, "BH")`` over them.  Relaxed contract: see :func:`gsea`."""
+    pathways in input order; ``padj = p.adjust(pval, "BH")`` over them.  Relaxed contract: see :func:`gsea`.  ``exact=True``:
+    ``pval`` and ``padj`` come from ``pval_exact`` of :func:`gsea`, and the simple estimator's is kept as the column ``pval_simple``."""
     import pandas as pd
 
     if names is None:
@@ -1114,16 +1175,19 @@ def fgsea(pathways: dict, stats, nsim: int = 1000, minSize=1, maxSize=np.inf, se
     if v.ndim != 1 or len(names) != len(v):
         raise ValueError("stats must hold one value per name")
     ptr, rows = _pathway_csr(pathways, names)
-    r = gsea(v, ptr, rows, nsim, minSize, maxSize, seed, False, ctx)
+    r = gsea(v, ptr, rows, nsim, minSize, maxSize, seed, False, ctx, exact=bool(exact))
     t = np.flatnonzero(r["tested"])
-    pv = r["pval"][t, 0]
-    return pd.DataFrame({"pathway": [n for n, k in zip(pathways, r["tested"]) if k], "pval": pv, "padj": p_adjust_fdr(pv), "ES": r["es"][t, 0],
-                         "NES": r["nes"][t, 0], "size": r["size"][t]})
+    pv = r["pval_exact" if exact else "pval"][t, 0]
+    out = pd.DataFrame({"pathway": [n for n, k in zip(pathways, r["tested"]) if k], "pval": pv, "padj": p_adjust_fdr(pv), "ES": r["es"][t, 0],
+                        "NES": r["nes"][t, 0], "size": r["size"][t]})
+    if exact:
+        out["pval_simple"] = r["pval"][t, 0]
+    return out
 
 
 def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = False, convertHu2Mm: bool = False, nt: int = 2, minSize=15,
             maxSize=np.inf, verbose: bool = True, seed: int = 180582, method: str = "GSEA", *, pathways=None, gene_names=None, gene_map=None,
-            ctx: Context | None = None) -> dict:
+            ctx: Context | None = None, exact: bool = False) -> dict:
     """``runGSEA(data, gmt.file, nsim, convertToEns, convertHu2Mm, nt, minSize, maxSize, verbose, seed, method)`` of the
     reference (R/pathwayAnalisys.R:65-96): gene-set enrichment of every cluster's ``data["cluster.gene.rnk"]`` column, all
     clusters in one device call (:func:`gsea`; the reference calls ``fgseaMultilevel(..., gseaParam = 0)`` per cluster).
@@ -1138,7 +1202,10 @@ def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = Fa
     (index: pathway names, columns: ``data["cluster.labels"]``) holding zeros where a pathway was not tested, ``fdr`` is
     Benjamini-Hochberg per cluster over the tested pathways, ``stat`` lists ``pathway, size`` of the tested pathways.
     Relaxed contract (include/gficf_gsea.h): ES and NES are fgsea's; the p-value is ``fgseaSimple``'s with ``nsim``
-    permutations, not the multilevel estimate; the random bits are this library's.
+    permutations, not the multilevel estimate; the random bits are this library's.  ``exact=True`` adds the tables ``ptail``,
+    ``pval_exact`` (see :func:`gsea`: the exact one-sided tail over a sampled probability of the sign, no floor at
+    ``1 / (nsim + 1)``) and ``fdr_exact``, Benjamini-Hochberg of ``pval_exact`` per cluster over the tested pathways; ``pval`` and
+    ``fdr`` stay the simple estimator's.
     """
     import pandas as pd
 
@@ -1166,13 +1233,18 @@ def runGSEA(data: dict, gmt_file=None, nsim: int = 1000, convertToEns: bool = Fa
     labels = list(range(stats.shape[1])) if labels is None else list(labels)
     ptr, rows = _pathway_csr(pathways, gene_names)
     tsmessage(f"GSEA of {len(pathways)} pathways in {stats.shape[1]} clusters, {int(nsim)} permutations", verbose=verbose)
-    r = gsea(stats, ptr, rows, nsim, minSize, maxSize, seed, False, ctx)
+    r = gsea(stats, ptr, rows, nsim, minSize, maxSize, seed, False, ctx, exact=bool(exact))
     t = np.flatnonzero(r["tested"])
-    fdr = np.zeros_like(r["pval"])
-    for c in range(stats.shape[1]):
-        fdr[t, c] = p_adjust_fdr(r["pval"][t, c])
+    cols = [("es", r["es"]), ("nes", r["nes"]), ("pval", r["pval"])]
+    for key, pv in (("fdr", r["pval"]),) + ((("fdr_exact", r["pval_exact"]),) if exact else ()):
+        fdr = np.zeros_like(pv)
+        for c in range(stats.shape[1]):
+            fdr[t, c] = p_adjust_fdr(pv[t, c])
+        cols.append((key, fdr))
+    if exact:
+        cols += [("ptail", r["ptail"]), ("pval_exact", r["pval_exact"])]
     names = list(pathways)
-    tab = {k: pd.DataFrame(v, index=names, columns=labels) for k, v in (("es", r["es"]), ("nes", r["nes"]), ("pval", r["pval"]), ("fdr", fdr))}
+    tab = {k: pd.DataFrame(v, index=names, columns=labels) for k, v in cols}
     data["gsea"] = {"pathways": pathways, **tab,
                     "stat": pd.DataFrame({"pathway": [names[i] for i in t], "size": r["size"][t]})}
     tsmessage("Done!", verbose=verbose)
@@ -3176,6 +3248,29 @@ class HipOps:
         from . import _tmm_lib
 
         check(_tmm_lib.load().gficf_tmm_sync(self._bind(), _tptr(ws)))
+
+    # -- exact tail of the enrichment score (libgficf_gsea_exact.so)
+    @staticmethod
+    def gsea_tail_workspace_bytes(G: int, n: int) -> int:
+        """Device scratch of ``gsea_tail`` for ``n`` pairs among ``G`` genes."""
+        from . import _gsea_exact_lib
+
+        return int(_gsea_exact_lib.load().gficf_gsea_tail_workspace_bytes(int(G), int(n)))
+
+    def gsea_tail(self, G, size, es, tail, ws):
+        """The exact one-sided tails on device-resident tensors: size int32, es and tail float64 of n, ws uint8 of
+        ``gsea_tail_workspace_bytes``.  Enqueues only: call ``gsea_tail_sync(ws)`` to wait and to collect the deferred input errors."""
+        from . import _gsea_exact_lib
+
+        if size.element_size() != 4 or es.element_size() != 8 or tail.element_size() != 8 or es.numel() != size.numel() or tail.numel() != size.numel():
+            raise ValueError("size must be int32, es and tail float64, all of one length")
+        check(_gsea_exact_lib.load().gficf_gsea_tail_device(self._bind(), int(G), int(size.numel()), _tptr(size), _tptr(es), _tptr(tail), _tptr(ws),
+                                                            int(ws.numel() * ws.element_size())))
+
+    def gsea_tail_sync(self, ws):
+        from . import _gsea_exact_lib
+
+        check(_gsea_exact_lib.load().gficf_gsea_tail_sync(self._bind(), _tptr(ws)))
 
     # -- highly variable genes (libgficf_hvg.so); every stage enqueues only: ``hvg_sync(ws)`` waits and collects the deferred errors
     @staticmethod
