@@ -1730,6 +1730,228 @@ def rsvd(A_csc_genes_x_cells, k: int, p: int = 10, q: int = 2, seed: int = 18058
     return {"d": d, "u": u, "v": genes, "cells": cells, "centre": mu}
 
 
+# ------------------------------------------------------------------ overdispersed genes (libgficf_od.so)
+_OD_COLUMNS = ("v", "fit", "res", "lp", "lpa", "qv", "gsf")
+_RAW_ABSENT = "Raw Counts absent! Please run gficf normalization with storeRaw = T"
+
+
+def _od_params(gam_k, sp, basis):
+    from . import _od_lib
+
+    if basis == "tp":
+        raise NotImplementedError('basis="tp" is mgcv\'s thin-plate regression spline (an eigen-truncation on a random subsample of knots), '
+                                  'which is not provided: pass basis="cr", the cubic regression spline (include/gficf_od.h)')
+    if basis != "cr":
+        raise ValueError('basis must be "cr"')
+    gam_k = int(gam_k)
+    if gam_k == 2 or gam_k > _od_lib.K_MAX:
+        raise ValueError(f"gam_k must be below 2 (the straight line) or 3 to {_od_lib.K_MAX} (the knots of the spline)")
+    sp = -1.0 if sp is None else float(sp)
+    if not sp >= 0 and sp != -1.0:
+        raise ValueError("sp must be None (the GCV search) or a smoothing parameter >= 0")
+    return gam_k, sp
+
+
+def _od_outputs(G: int) -> dict:
+    from . import _od_lib
+
+    o = {k: np.full(G, np.nan, dtype=np.float64) for k in _OD_COLUMNS}
+    o["valid"] = np.zeros(G, dtype=np.int32)
+    o["info"] = np.full(len(_od_lib.INFO), np.nan, dtype=np.float64)
+    return o
+
+
+def _od_result(o: dict, m, var, nobs) -> dict:
+    from . import _od_lib
+
+    info = dict(zip(_od_lib.INFO, o["info"]))
+    kk = int(info["basis"])
+    r = {"m": m, "var": var, "nobs": nobs, "valid": o["valid"] != 0}
+    r.update({k: o[k] for k in _OD_COLUMNS})
+    r.update({"n": int(info["n"]), "u": int(info["u"]), "basis": kk, "knots": o["info"][8:8 + kk].copy(), "lambda": float(info["lambda"]),
+              "gcv": float(info["gcv"]), "edf": float(info["edf"]), "vbar": float(info["vbar"]), "rss": float(info["rss"])})
+    return r
+
+
+def over_dispersed_from_moments(m, var, nobs, N: int, gam_k: int = 5, min_gene_cells: int = 0, max_adjusted_variance: float = 1e3,
+                                min_adjusted_variance: float = 1e-3, basis: str = "cr", sp=None, ctx: Context | None = None) -> dict:
+    """Steps 1 - 6 of :func:`findOverDispersed` (include/gficf_od.h) from the genes' ICF weight ``m``, the variance ``var`` and
+    the non-zero count ``nobs`` of their raw counts over ``N`` cells: ``v = log(var)``, ``valid``, the spline ``fit`` (NaN at an
+    invalid gene), ``res``, ``lp``, ``lpa``, ``qv``, ``gsf`` per gene, and the fit's ``n``, ``u``, ``basis`` (the columns used:
+    ``gam_k``, or 2 for the straight line, 1 for the mean), ``knots``, ``lambda``, ``gcv``, ``edf``, ``vbar``, ``rss``."""
+    from . import _od_lib
+
+    gam_k, sp = _od_params(gam_k, sp, basis)
+    m, var = _hvg_vectors(m, var)
+    nobs = np.ascontiguousarray(nobs, dtype=np.int32)
+    if nobs.shape != m.shape:
+        raise ValueError("m, var and nobs must be vectors of one length")
+    if int(N) < 2:
+        raise ValueError("the variance of a gene needs at least 2 cells")
+    o = _od_outputs(len(m))
+    ctx = ctx or default_context()
+    check(_od_lib.load().gficf_od_from_moments_host(ctx.handle, len(m), int(N), _np_ptr(m), _np_ptr(var), _np_ptr(nobs), gam_k, int(min_gene_cells),
+                                                    float(min_adjusted_variance), float(max_adjusted_variance), sp, _np_ptr(o["v"]), _np_ptr(o["valid"]),
+                                                    _np_ptr(o["fit"]), _np_ptr(o["res"]), _np_ptr(o["lp"]), _np_ptr(o["lpa"]), _np_ptr(o["qv"]),
+                                                    _np_ptr(o["gsf"]), _np_ptr(o["info"])))
+    return _od_result(o, m, var, nobs)
+
+
+def findOverDispersed(data: dict, gam_k: int = 5, alpha: float = .05, use_unadjusted_pvals: bool = False, max_adjusted_variance: float = 1e3,
+                      min_adjusted_variance: float = 1e-3, verbose: bool = True, min_gene_cells: int = 0, basis: str = "cr", sp=None,
+                      ret_stages: bool = False, ctx: Context | None = None):
+    """``findOverDispersed(data, gam.k, alpha, ...)`` of the reference (R/dimensinalityReduction.R:235-291, after pagoda2) on
+    the device, under the contract of include/gficf_od.h: every gene's log variance (of ``data["rawCounts"]``) regressed on its
+    ICF weight ``data["w"]`` with a penalised spline of ``gam_k`` knots, the F-test log p-value ``lp`` of its residual, its BH
+    adjustment in log space ``lpa``, the chi-square adjusted variance ``qv`` and the gene scale factor ``gsf``.  STATED
+    DIFFERENCE: the spline is mgcv's cubic regression spline (``basis="cr"``, ``s(m, k, bs = "cr")`` with GCV), not its default
+    thin-plate basis (``basis="tp"`` raises); ``sp`` fixes the smoothing parameter.  Returns a ``pandas.DataFrame`` with the
+    columns ``m, v, nobs, res, lp, lpa, qv, gsf``, one row per row of ``data["gficf"]``.  ``ret_stages=True``: a dictionary with
+    that ``table`` and ``fit, valid, knots, lambda, gcv, edf, n, u, basis`` and ``ods``, the rows below ``log(alpha)`` (of ``lpa``,
+    or of ``lp`` with ``use_unadjusted_pvals``).  ``plot`` is not provided."""
+    import pandas as pd
+
+    from . import _od_lib
+
+    gam_k, sp = _od_params(gam_k, sp, basis)
+    if data.get("rawCounts") is None:
+        raise ValueError(_RAW_ABSENT)
+    tsmessage("calculating variance fit ...", verbose=verbose)
+    M, colptr, rowidx, x = _csc_parts(data["rawCounts"])
+    G, N = M.shape
+    m = np.ascontiguousarray(data["w"], dtype=np.float64)
+    if m.shape != (G,) or data["gficf"].shape[0] != G:
+        raise ValueError("data['w'] and data['gficf'] must hold one entry per row of data['rawCounts']")
+    if N < 2:
+        raise ValueError("the variance of a gene needs at least 2 cells")
+    o = _od_outputs(G)
+    var, nobs = np.zeros(G, dtype=np.float64), np.zeros(G, dtype=np.int32)
+    ctx = ctx or default_context()
+    check(_od_lib.load().gficf_od_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x), _np_ptr(m),
+                                       gam_k, int(min_gene_cells), float(min_adjusted_variance), float(max_adjusted_variance), sp, _np_ptr(var),
+                                       _np_ptr(nobs), _np_ptr(o["v"]), _np_ptr(o["valid"]), _np_ptr(o["fit"]), _np_ptr(o["res"]), _np_ptr(o["lp"]),
+                                       _np_ptr(o["lpa"]), _np_ptr(o["qv"]), _np_ptr(o["gsf"]), _np_ptr(o["info"])))
+    r = _od_result(o, m, var, nobs)
+    tsmessage(" using lm " if r["basis"] <= 2 else " using gam ", verbose=verbose)
+    ods = np.flatnonzero((r["lp"] if use_unadjusted_pvals else r["lpa"]) < np.log(alpha))
+    tsmessage(f"{len(ods)}overdispersed genes ...{len(ods)}", verbose=verbose)
+    tsmessage("done.\n", verbose=verbose)
+    table = pd.DataFrame({k: r[k] for k in ("m", "v", "nobs", "res", "lp", "lpa", "qv", "gsf")})
+    if not ret_stages:
+        return table
+    out = {k: r[k] for k in ("fit", "valid", "var", "knots", "lambda", "gcv", "edf", "n", "u", "basis", "vbar", "rss")}
+    out.update({"table": table, "ods": ods})
+    return out
+
+
+def _od_dev(device: int):
+    ops = _umap_hip(device)
+    tc = ops.torch
+    dev = tc.device("cuda", device)
+    return ops, tc, dev, (lambda v, dt=np.float64: tc.from_numpy(np.array(v, dtype=dt, order="C")).to(dev))
+
+
+def log_pf(res, df, device: int = 0) -> np.ndarray:
+    """``pf(exp(res), df, df, lower.tail = FALSE, log.p = TRUE)`` in log space (step 3 of include/gficf_od.h): the log of the
+    regularised incomplete beta ``I_z(df / 2, df / 2)`` at ``z = 1 / (1 + exp(res))``, far into either tail.  ``res = -Inf``
+    gives 0, ``df = 0`` NaN."""
+    res = np.ascontiguousarray(res, dtype=np.float64)
+    a = np.array(np.broadcast_to(np.asarray(df, dtype=np.float64) / 2.0, res.shape), dtype=np.float64, order="C")
+    if res.size == 0:
+        return np.zeros(res.shape)
+    ops, tc, dev, t = _od_dev(device)
+    ws = tc.zeros(ops.od_workspace_bytes(res.size), dtype=tc.uint8, device=dev)
+    out = tc.empty(res.size, dtype=tc.float64, device=dev)
+    ops.od_logpf(t(res.ravel()), t(a.ravel()), ws, out)
+    ops.od_sync(ws)
+    return out.cpu().numpy().reshape(res.shape)
+
+
+def log_qchisq(lp, df: float, device: int = 0) -> np.ndarray:
+    """``qchisq(lp, df, lower.tail = FALSE, log.p = TRUE)`` (step 5 of include/gficf_od.h): the ``x`` whose upper chi-square
+    tail has the log probability ``lp``, by Newton in log space.  ``lp = 0`` gives 0, ``lp = -Inf`` Inf; ``lp > 0`` or NaN, or
+    ``df <= 0``, NaN.  A value whose iteration hits its cap raises."""
+    lp = np.ascontiguousarray(lp, dtype=np.float64)
+    if lp.size == 0:
+        return np.zeros(lp.shape)
+    ops, tc, dev, t = _od_dev(device)
+    ws = tc.zeros(ops.od_workspace_bytes(lp.size), dtype=tc.uint8, device=dev)
+    out = tc.empty(lp.size, dtype=tc.float64, device=dev)
+    ops.od_logqchisq(t(lp.ravel()), float(df), ws, out)
+    ops.od_sync(ws)
+    return out.cpu().numpy().reshape(lp.shape)
+
+
+def bh_adjust_log(lp, device: int = 0) -> np.ndarray:
+    """``bh.adjust(lp, log = TRUE)`` of the reference (R/dimensinalityReduction.R:294-308), literally, on the device: over the
+    non-NaN ``lp`` in ascending order (ties by position) ``lp + log(n / rank)``, the running minimum from the end; NaN stays."""
+    lp = np.ascontiguousarray(lp, dtype=np.float64)
+    if lp.ndim != 1 or len(lp) < 1:
+        raise ValueError("lp must be a vector")
+    ops, tc, dev, t = _od_dev(device)
+    ws = tc.zeros(ops.od_workspace_bytes(len(lp)), dtype=tc.uint8, device=dev)
+    out = tc.empty(len(lp), dtype=tc.float64, device=dev)
+    ops.od_bh_log(t(lp), ws, out)
+    ops.od_sync(ws)
+    return out.cpu().numpy()
+
+
+def select_scale_rows(M, rows=None, scale=None, ctx: Context | None = None):
+    """The rows ``rows`` of the genes x cells matrix ``M`` (scipy sparse), renumbered in ascending order, each multiplied by
+    its entry of ``scale`` (one per row of ``M``; None: 1), as a scipy CSC matrix: ``x[, odgenes]`` and ``x@x * gsf`` of the
+    reference's ``runPCA`` in one pass on the device.  An entry whose scale is 0 stays stored, as 0.  ``rows=None``: every row
+    (only the values change).  Selecting no row is an error, not an empty decomposition."""
+    import scipy.sparse as sp
+
+    from . import _od_lib
+
+    M, colptr, rowidx, x = _csc_parts(M)
+    G, N = M.shape
+    mask = None
+    if rows is not None:
+        rows = np.asarray(rows, dtype=np.int64).ravel()
+        if len(rows) == 0:
+            raise ValueError("select_scale_rows: no row is selected: there is nothing to decompose")
+        if rows.min() < 0 or rows.max() >= G or len(np.unique(rows)) != len(rows):
+            raise ValueError(f"rows must name distinct rows of M (0 .. {G - 1})")
+        mask = np.zeros(G, dtype=np.int32)
+        mask[rows] = 1
+    if scale is not None:
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        if scale.shape != (G,):
+            raise ValueError("scale must hold one value per row of M")
+    if G < 1:
+        raise ValueError("M must hold at least one row")
+    nnz = len(x)
+    out_x = np.zeros(max(nnz, 1), dtype=np.float64)
+    out_cp = np.zeros(N + 1, dtype=np.int64)
+    out_row = np.zeros(max(nnz, 1), dtype=np.int32)
+    nsel = np.zeros(1, dtype=np.int32)
+    ctx = ctx or default_context()
+    check(_od_lib.load().gficf_od_select_scale_host(ctx.handle, G, N, _np_ptr(colptr), 1 if colptr.dtype == np.int64 else 0, _np_ptr(rowidx), _np_ptr(x),
+                                                    _np_ptr(mask), _np_ptr(scale), _np_ptr(out_cp), _np_ptr(out_row), _np_ptr(out_x), _np_ptr(nsel)))
+    if mask is None:
+        return sp.csc_matrix((out_x[:nnz], rowidx, colptr), shape=(G, N))
+    n_out = int(out_cp[N])
+    return sp.csc_matrix((out_x[:n_out], out_row[:n_out], out_cp.astype(colptr.dtype)), shape=(int(nsel[0]), N))
+
+
+def odgenes_rows(overD, n_odgenes=None) -> np.ndarray:
+    """The rows ``runPCA(use.odgenes = T, n.odgenes)`` of the reference decomposes (R/dimensinalityReduction.R:103-113), in
+    ascending order: those with ``lpa < log(0.1)``; with ``n_odgenes`` at most that many, the first ``n_odgenes`` of them in row
+    order (the reference's own quirk); with ``n_odgenes`` more than that many, the ``min(G, n_odgenes)`` rows of smallest ``lp``
+    (ordered stably, NaN last).  ``overD``: the table of :func:`findOverDispersed`."""
+    lp, lpa = np.asarray(overD["lp"], dtype=np.float64), np.asarray(overD["lpa"], dtype=np.float64)
+    rows = np.flatnonzero(lpa < np.log(0.1))
+    if n_odgenes is not None:
+        n_odgenes = int(n_odgenes)
+        if n_odgenes > len(rows):
+            rows = np.argsort(lp, kind="stable")[:min(len(lp), n_odgenes)]
+        else:
+            rows = rows[:n_odgenes]
+    return np.sort(rows).astype(np.int64)
+
+
 def _pca_dim(data: dict, dim):
     if dim is None:
         if data.get("dimPCA") is None:
@@ -1740,41 +1962,75 @@ def _pca_dim(data: dict, dim):
 
 
 def _pca_unsupported(var_scale, use_odgenes, randomized):
-    if use_odgenes or var_scale:
+    for name, value in (("use_odgenes", use_odgenes), ("var_scale", var_scale)):
+        if isinstance(value, str) and value != "cr":
+            raise ValueError(f'{name} must be False or "cr"')
+    if any(v and not isinstance(v, str) for v in (use_odgenes, var_scale)):
         raise NotImplementedError("use_odgenes / var_scale need findOverDispersed (the mgcv::gam fit of the reference), which is not "
-                                  "provided: pass use_odgenes=False and var_scale=False")
+                                  "provided on mgcv's default thin-plate basis: pass use_odgenes=\"cr\" / var_scale=\"cr\" for the same model "
+                                  "on its cubic regression spline (include/gficf_od.h), or use_odgenes=False and var_scale=False")
     if not randomized:
         raise NotImplementedError("randomized=False is the reference's full decomposition (RSpectra::svds / prcomp), which is not "
                                   "provided: pass randomized=True")
 
 
-def runPCA(data: dict, dim=None, var_scale: bool = False, centre: bool = False, randomized: bool = True, seed: int = 180582,
-           use_odgenes: bool = False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
+def _pca_matrix(data: dict, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx):
+    """The matrix ``runPCA`` / ``runLSA`` decompose and what they store about it (R/dimensinalityReduction.R:103-122): with
+    ``use_odgenes="cr"`` the overdispersed rows (:func:`odgenes_rows`), with ``var_scale="cr"`` every row times its ``gsf``."""
+    if not use_odgenes and not var_scale:
+        return data["gficf"], {}
+    if plot_odgenes:
+        warnings.warn("plot_odgenes=True (the reference's smoothScatter plots) is not provided: ignored", stacklevel=3)
+    overD = findOverDispersed(data, alpha=0.1, verbose=False, ctx=ctx)
+    G = data["gficf"].shape[0]
+    rows = odgenes_rows(overD, n_odgenes) if use_odgenes else np.arange(G, dtype=np.int64)
+    if use_odgenes:
+        if len(rows) == 0:
+            raise ValueError("use_odgenes: no gene is overdispersed (lpa < log(0.1)): there is nothing to decompose; pass n_odgenes")
+        tsmessage("... using ", len(rows), " OD genes", verbose=True)
+    scale = np.ascontiguousarray(overD["gsf"], dtype=np.float64) if var_scale else None
+    M = select_scale_rows(data["gficf"], rows if use_odgenes else None, scale, ctx)
+    return M, {"odgenes": overD, "gene_rows": rows}
+
+
+def runPCA(data: dict, dim=None, var_scale=False, centre: bool = False, randomized: bool = True, seed: int = 180582,
+           use_odgenes=False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
     """``runPCA(data, dim, var.scale, centre, randomized, seed, use.odgenes, n.odgenes, plot.odgenes)`` of the reference
     (R/dimensinalityReduction.R:85-133): ``rsvd::rpca(t(data$gficf), k = dim, center = centre, scale = F)`` on the device
     (:func:`rsvd`, relaxed contract).  ``data["pca"]`` becomes ``{"cells": N x dim (rpca's x), "genes": G x dim (its rotation),
     "centre": centre, "rescale": var_scale}`` plus ``"mean"``, the gene means that were subtracted (None without ``centre``; the
-    reference's centring densifies and keeps nothing for later), and ``data["dimPCA"] = dim``."""
+    reference's centring densifies and keeps nothing for later), and ``data["dimPCA"] = dim``.
+
+    ``use_odgenes="cr"`` decomposes only the overdispersed genes of :func:`findOverDispersed` (:func:`odgenes_rows`, in
+    ascending row order: where the reference decomposes in ``order(lp)`` order the result is a permutation of the same
+    columns), ``var_scale="cr"`` scales every gene by its ``gsf`` first; either alone or both (:func:`select_scale_rows`).
+    ``data["pca"]`` then also holds ``"odgenes"`` (the table) and ``"gene_rows"`` (the rows of ``data["gficf"]`` decomposed,
+    one per row of ``"genes"``), which :func:`pca_project` applies to new cells.  ``True`` stands for the reference's fit on
+    mgcv's default thin-plate basis, which is not provided.  ``plot_odgenes`` is accepted and ignored, with a warning."""
     if use_odgenes and data.get("rawCounts") is None:
-        raise ValueError("Raw Counts absent! Please run gficf normalization with storeRaw = T")
+        raise ValueError(_RAW_ABSENT)
     dim = _pca_dim(data, dim)
     _pca_unsupported(var_scale, use_odgenes, randomized)
-    r = rsvd(data["gficf"], dim, seed=seed, centre=bool(centre), ctx=ctx)
+    M, extra = _pca_matrix(data, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx)
+    r = rsvd(M, dim, seed=seed, centre=bool(centre), ctx=ctx)
     data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": bool(centre), "rescale": bool(var_scale), "mean": r["centre"]}
+    data["pca"].update(extra)
     return data
 
 
-def runLSA(data: dict, dim=None, var_scale: bool = False, centre: bool = False, randomized: bool = True, seed: int = 180582,
-           use_odgenes: bool = False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
+def runLSA(data: dict, dim=None, var_scale=False, centre: bool = False, randomized: bool = True, seed: int = 180582,
+           use_odgenes=False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
     """``runLSA(...)`` of the reference (R/dimensinalityReduction.R:19-65): ``rsvd::rsvd(t(data$gficf), k = dim)``, then
     ``cells = u %*% diag(d)`` and ``genes = v``.  As in the reference ``centre`` is accepted and not used
-    (``data$pca$centre <- F``, :59)."""
+    (``data$pca$centre <- F``, :59).  ``use_odgenes="cr"`` / ``var_scale="cr"``: as in :func:`runPCA`."""
     if use_odgenes and data.get("rawCounts") is None:
-        raise ValueError("Raw Counts absent! Please run gficf normalization with storeRaw = T")
+        raise ValueError(_RAW_ABSENT)
     dim = _pca_dim(data, dim)
     _pca_unsupported(var_scale, use_odgenes, randomized)
-    r = rsvd(data["gficf"], dim, seed=seed, centre=False, ctx=ctx)
+    M, extra = _pca_matrix(data, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx)
+    r = rsvd(M, dim, seed=seed, centre=False, ctx=ctx)
     data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": False, "rescale": bool(var_scale), "mean": None}
+    data["pca"].update(extra)
     return data
 
 
@@ -1830,11 +2086,23 @@ def pca_project(data: dict, gficf_new, ctx: Context | None = None) -> np.ndarray
     """``x %*% data$pca$genes`` of ``embedNewCells`` (reference R/cellClassifier.R:54-64) for ``gficf_new``, the genes x
     new-cells GF-ICF matrix of :func:`gficf_with_weights` over the genes of ``data["pca"]["genes"]``: the new cells in the PCA
     space, n_new x dim.  After ``runPCA(centre=True)`` the training gene means are subtracted first (the reference's
-    ``scaleMatrix`` is a stub that does nothing)."""
+    ``scaleMatrix`` is a stub that does nothing).  After ``use_odgenes="cr"`` / ``var_scale="cr"`` (``data["pca"]["gene_rows"]``)
+    ``gficf_new`` has one row per row of ``data["gficf"]``: the rows decomposed are selected and, with ``rescale``, scaled by
+    the stored ``gsf`` first (:func:`select_scale_rows`; reference R/cellClassifier.R:56-62)."""
     from . import _pca_lib
 
     if data.get("pca") is None:
         raise ValueError("First run runPCA or runLSA to reduce dimensionality")
+    if data["pca"].get("gene_rows") is not None:
+        od = data["pca"]["odgenes"]
+        G_all = len(od["gsf"])
+        if gficf_new.shape[0] != G_all:
+            raise ValueError("gficf_new must have one row per row of data['gficf'] (data['pca']['odgenes'])")
+        rows = np.asarray(data["pca"]["gene_rows"], dtype=np.int64)
+        scale = np.ascontiguousarray(od["gsf"], dtype=np.float64) if data["pca"].get("rescale") else None
+        every = len(rows) == G_all
+        if scale is not None or not every:
+            gficf_new = select_scale_rows(gficf_new, None if every else rows, scale, ctx)
     genes = np.asfortranarray(data["pca"]["genes"], dtype=np.float64)
     M, colptr, rowidx, x = _csc_parts(gficf_new)
     G, n_new = M.shape
@@ -3341,6 +3609,72 @@ class HipOps:
         from . import _hvg_lib
 
         check(_hvg_lib.load().gficf_hvg_sync(self._bind(), _tptr(ws)))
+
+    # -- overdispersed genes (libgficf_od.so); ``ws``: uint8 of ``od_workspace_bytes``, its first word zero before the first stage
+    # (``torch.zeros``); ``od_fit`` and ``od_bh_log`` wait once for their host stage, the others only enqueue; ``od_sync(ws)``
+    # waits and collects the deferred errors.  od_fit -> od_scores -> od_bh_log -> od_select_scale -> rsvd never leave the device.
+    @staticmethod
+    def od_workspace_bytes(G: int, N: int = 0) -> int:
+        """Device scratch of the ``od_*`` stages for lists of up to ``G`` values and, for ``od_select_scale``, ``N`` columns."""
+        from . import _od_lib
+
+        return int(_od_lib.load().gficf_od_workspace_bytes(int(G), int(N)))
+
+    def od_fit(self, m, var, nobs, ws, v, valid, fit, res, gam_k: int = 5, min_gene_cells: int = 0, sp=None) -> dict:
+        """Steps 1 - 3 up to ``res`` (m, var float64 and nobs int32 of G; v, fit, res float64 and valid int32 of G).  Returns
+        the fit's scalars (``_od_lib.INFO``)."""
+        from . import _od_lib
+
+        info = np.full(len(_od_lib.INFO), np.nan, dtype=np.float64)
+        check(_od_lib.load().gficf_od_fit_device(self._bind(), int(m.numel()), _tptr(m), _tptr(var), _tptr(nobs), int(gam_k), int(min_gene_cells),
+                                                 -1.0 if sp is None else float(sp), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(v),
+                                                 _tptr(valid), _tptr(fit), _tptr(res), _np_ptr(info)))
+        return dict(zip(_od_lib.INFO, info))
+
+    def od_logpf(self, res, a, ws, lp):
+        """``lp = log I_z(a, a)`` at ``z = 1 / (1 + exp(res))``, elementwise (float64)."""
+        from . import _od_lib
+
+        check(_od_lib.load().gficf_od_logpf_device(self._bind(), int(res.numel()), _tptr(res), _tptr(a), _tptr(ws), int(ws.numel() * ws.element_size()),
+                                                   _tptr(lp)))
+
+    def od_logqchisq(self, lp, df, ws, x):
+        """``x = qchisq(lp, df, lower.tail = FALSE, log.p = TRUE)``, elementwise (float64)."""
+        from . import _od_lib
+
+        check(_od_lib.load().gficf_od_logqchisq_device(self._bind(), int(lp.numel()), _tptr(lp), float(df), _tptr(ws),
+                                                       int(ws.numel() * ws.element_size()), _tptr(x)))
+
+    def od_scores(self, res, nobs, v, N, ws, lp, qv, gsf, min_adjusted_variance: float = 1e-3, max_adjusted_variance: float = 1e3):
+        """Steps 3, 5, 6: ``lp``, ``qv``, ``gsf`` (float64 of G) from ``res``, ``nobs`` (int32), ``v`` and the number of cells."""
+        from . import _od_lib
+
+        check(_od_lib.load().gficf_od_scores_device(self._bind(), int(res.numel()), _tptr(res), _tptr(nobs), _tptr(v), int(N), float(min_adjusted_variance),
+                                                    float(max_adjusted_variance), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(lp), _tptr(qv),
+                                                    _tptr(gsf)))
+
+    def od_bh_log(self, lp, ws, lpa):
+        """Step 4: ``lpa = bh.adjust(lp, log = TRUE)`` (float64 of G)."""
+        from . import _od_lib
+
+        check(_od_lib.load().gficf_od_bh_log_device(self._bind(), int(lp.numel()), _tptr(lp), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(lpa)))
+
+    def od_select_scale(self, G, n_cells, colptr, rowidx, x, mask, scale, ws, out_colptr, out_rowidx, out_x, nsel):
+        """The rows with ``mask != 0`` (int32 of G; None: all, only ``out_x`` is written) of the G x n_cells CSC (colptr int64),
+        renumbered and multiplied by ``scale`` (float64 of G; None: 1): ``out_colptr`` int64 of n_cells + 1, ``out_rowidx``
+        int32 and ``out_x`` float64 with room for the input's entries, ``nsel`` int32 of 1."""
+        from . import _od_lib
+
+        if colptr.element_size() != 8:
+            raise ValueError("colptr must be int64")
+        check(_od_lib.load().gficf_od_select_scale_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x), int(x.numel()),
+                                                          _tptr(mask), _tptr(scale), _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(out_colptr),
+                                                          _tptr(out_rowidx), _tptr(out_x), _tptr(nsel)))
+
+    def od_sync(self, ws):
+        from . import _od_lib
+
+        check(_od_lib.load().gficf_od_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def rsvd_workspace_bytes(G: int, N: int, nnz: int, l: int) -> int:
