@@ -267,52 +267,36 @@ int launch_ingest(gficf_ctx* ctx, const T* d_idx, int64_t n_rows, int k, int64_t
   static const bool use_reg = getenv("GFICF_JACCARD_INGEST_REG") != nullptr;     // test hook: the one-thread-per-cell variant
   // rows taken to hold distinct ids (gficf_ctx_set_jaccard_distinct): no duplicate scan; not for sub-problems in local ids
   const bool scan = !(ctx->jaccard_assume_distinct && zero_ok == 0);
-#define LAUNCH_INGEST_REG(KP, CM)                                                                                          \
-  do {                                                                                                                     \
-    if (use_reg)                                                                                                           \
-      hipLaunchKernelGGL((k_ingest_reg<T, KP, CM>), dim3(grid2), dim3(INGEST2_ROWS), 0, ctx->stream, d_idx, n_rows, k, ld, N_total, \
-                         table, ctx->d_status, zero_ok);                                                                   \
-    else if (scan)                                                                                                         \
-      hipLaunchKernelGGL((k_ingest_tile<T, KP, CM>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, n_rows, k, ld, N_total,  \
-                         table, ctx->d_status, zero_ok, gficf_halo_map{});                                                 \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((k_ingest_tile<T, KP, CM, false, false>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, n_rows, k, ld, N_total, \
-                         table, ctx->d_status, zero_ok, gficf_halo_map{});                                                 \
-  } while (0)
-#define LAUNCH_INGEST(KP, CM)                                                                                   \
-  hipLaunchKernelGGL((k_ingest<T, KP, CM>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, n_rows, k, ld, N_total, \
-                     table, ctx->d_status, zero_ok, scan ? 1 : 0)
-  switch (f.kpad) {
-    case 16: LAUNCH_INGEST_REG(16, false); break;
-    case 32: if (f.compact) LAUNCH_INGEST_REG(32, true); else LAUNCH_INGEST_REG(32, false); break;
-    case 64:
-      if (f.dual) {                                          // dual rows: the tile kernel writes both parts of every row
-        if (scan)
-          hipLaunchKernelGGL((k_ingest_tile<T, 64, true, false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, n_rows, k, ld, N_total,
-                             table, ctx->d_status, zero_ok, gficf_halo_map{});
-        else
-          hipLaunchKernelGGL((k_ingest_tile<T, 64, true, false, false, true>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, n_rows, k, ld, N_total,
-                             table, ctx->d_status, zero_ok, gficf_halo_map{});
-      } else if (f.compact) LAUNCH_INGEST_REG(64, true); else LAUNCH_INGEST_REG(64, false);
-      break;
-    case 128: if (f.compact) LAUNCH_INGEST(128, true); else LAUNCH_INGEST(128, false); break;
-    default: if (f.compact) LAUNCH_INGEST(256, true); else LAUNCH_INGEST(256, false); break;
-  }
-#undef LAUNCH_INGEST
-#undef LAUNCH_INGEST_REG
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  auto tile = [&](auto KPAD, auto CMP, auto DUAL) {
+    return with_flag(scan, [&](auto SCAN) {
+      return launch_grid<k_ingest_tile<T, KPAD, CMP, false, SCAN, DUAL>>(ctx, dim3(grid), dim3(256), 0, d_idx, n_rows, k, ld, N_total, table,
+                                                                      ctx->d_status, zero_ok, gficf_halo_map{});
+    });
+  };
+  if (f.dual) return tile(std::integral_constant<int, 64>{}, std::true_type{}, std::true_type{});   // writes both parts of every row
+  return with_table_fmt(f, [&](auto KPAD, auto CMP) {
+    if constexpr (KPAD > 64)                                 // (neither the tile nor the register form holds a row this long)
+      return launch_grid<k_ingest<T, KPAD, CMP>>(ctx, dim3(grid), dim3(256), 0, d_idx, n_rows, k, ld, N_total, table, ctx->d_status, zero_ok,
+                                                 scan ? 1 : 0);
+    else if (use_reg)
+      return launch_grid<k_ingest_reg<T, KPAD, CMP>>(ctx, dim3(grid2), dim3(INGEST2_ROWS), 0, d_idx, n_rows, k, ld, N_total, table, ctx->d_status,
+                                                     zero_ok);
+    else
+      return tile(KPAD, CMP, std::false_type{});
+  });
 }
 
 // workgroups per CU for an edge kernel: as many as fit, up to 8 (measured at 100 k x 30, tools/r02_sweep.sh: 4 per CU 44-47 us,
 // 6: 43-46, 8: 41-42, 10-12: 40-42 — the row gathers are latency-bound, more waves keep more of them in flight).  Asked of the
-// runtime for the kernel that is launched (the pipelined and the general form differ in registers), once per kernel.
-template <typename K>
-int edge_blocks_per_cu(K kernel, int threads, size_t lds_bytes, std::atomic<int>& cache, int* out) {
+// runtime for the kernel that is launched (the pipelined and the general form differ in registers), once per kernel: the cache
+// is this function's own, so a kernel cannot be paired with another one's.
+template <auto Kernel>
+int resident_blocks_per_cu(int threads, size_t lds_bytes, int* out) {
+  static std::atomic<int> cache{0};
   int v = cache.load(std::memory_order_relaxed);
   if (v == 0) {
     int nb = 0;
-    GFICF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds_bytes));
+    GFICF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, lds_bytes));
     v = nb > 8 ? 8 : nb > 0 ? nb : 1;
     if (const char* e = getenv("GFICF_JACCARD_BLOCKS_PER_CU")) {   // tuning knob
       const int t = atoi(e);
@@ -324,139 +308,82 @@ int edge_blocks_per_cu(K kernel, int threads, size_t lds_bytes, std::atomic<int>
   return GFICF_OK;
 }
 
-template <int KPAD, bool BIG, bool CMP, int OUT, bool MAP>
-int launch_edges_m(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  using C = JCfg<KPAD, CMP>;
-  // grid = what is resident at once (occupancy x CUs); waves stride over the cells
-  static std::atomic<int> bpc_general{0}, bpc_pipe{0}, bpc_pipe_nob16{0};
-  constexpr size_t lds_bytes = edges_lds_bytes<KPAD, CMP>();
+// grid = what is resident at once (occupancy x CUs), at most one workgroup per work item; the waves stride over the cells.
+// xcd: the kernel renumbers its workgroups by XCD (xcd_block), which takes a grid of whole eights (surplus workgroups find no cell and leave)
+template <auto Kernel, typename... A>
+int launch_resident(gficf_ctx* ctx, int threads, size_t lds_bytes, int64_t work_items, uint32_t xcd, A... args) {
   int blocks_per_cu = 1;
+  const int rc = resident_blocks_per_cu<Kernel>(threads, lds_bytes, &blocks_per_cu);
+  if (rc) return rc;
+  const int64_t cap = (int64_t)ctx->num_cus * blocks_per_cu;
+  unsigned grid = (unsigned)(work_items < cap ? work_items : cap);
+  if (xcd && grid > 8) grid = (grid + 7u) & ~7u;
+  return launch_grid<Kernel>(ctx, dim3(grid), dim3(threads), lds_bytes, args...);
+}
+
+// hash-set rows: the pipelined kernel where it exists (k <= 32: row i in one register, at most four steps), else the general one
+template <int KPAD, bool BIG, bool CMP, int OUT, bool MAP>
+int launch_edges_hash(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, const EdgeOut& o) {
+  using C = JCfg<KPAD, CMP>;
+  constexpr size_t lds_bytes = edges_lds_bytes<KPAD, CMP>();
   static const bool no_pipe = getenv("GFICF_JACCARD_NO_PIPE") != nullptr;        // test hook: the one-cell-at-a-time kernel for every k
   if constexpr (C::EPL == 1 && C::SPQ <= 4) {
     if (!no_pipe) {
+      const int64_t quads = gficf_ceil_div(gficf_ceil_div(ce - cb, 4), C::WAVES);       // a wave takes four cells at a time
       const bool nob16 = CMP && N < 65536;     // no id carries bit 16: the kernel variant that does not look for it (configs 1-3 of BASELINE.json)
-      int rc;
-      if constexpr (!MAP) {
-        if (o.dup_status != nullptr) {           // a table without row flags (gficf_ctx_set_jaccard_distinct)
-          static std::atomic<int> bpc_nf{0}, bpc_nf_nob16{0};
-          if (nob16) rc = edge_blocks_per_cu(k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, !CMP, false, true>, C::WAVES * 64, lds_bytes, bpc_nf_nob16, &blocks_per_cu);
-          else rc = edge_blocks_per_cu(k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, true, false, true>, C::WAVES * 64, lds_bytes, bpc_nf, &blocks_per_cu);
-          if (rc) return rc;
-          const int64_t cap_n = (int64_t)ctx->num_cus * blocks_per_cu;
-          const int64_t need_n = gficf_ceil_div(gficf_ceil_div(ce - cb, 4), C::WAVES);
-          unsigned grid_n = (unsigned)(need_n < cap_n ? need_n : cap_n);
-          if (o.xcd && grid_n > 8) grid_n = (grid_n + 7u) & ~7u;
-          if (nob16)
-            hipLaunchKernelGGL((k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, !CMP, false, true>), dim3(grid_n), dim3(C::WAVES * 64), lds_bytes, ctx->stream,
-                               table, N, k, cb, ce, o);
-          else
-            hipLaunchKernelGGL((k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, true, false, true>), dim3(grid_n), dim3(C::WAVES * 64), lds_bytes, ctx->stream,
-                               table, N, k, cb, ce, o);
-          GFICF_HIP_CHECK(hipGetLastError());
-          return GFICF_OK;
+      return with_flag(nob16, [&](auto NOB16) {
+        auto pipe = [&](auto NOFLAG) {
+          return launch_resident<k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, !(CMP && NOB16), MAP, NOFLAG>>(ctx, C::WAVES * 64, lds_bytes, quads, o.xcd,
+                                                                                                       table, N, k, cb, ce, o);
+        };
+        if constexpr (!MAP) {
+          if (o.dup_status != nullptr) return pipe(std::true_type{});           // a table without row flags (gficf_ctx_set_jaccard_distinct)
         }
-      }
-      if (nob16) rc = edge_blocks_per_cu(k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, !CMP, MAP>, C::WAVES * 64, lds_bytes, bpc_pipe_nob16, &blocks_per_cu);
-      else rc = edge_blocks_per_cu(k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, true, MAP>, C::WAVES * 64, lds_bytes, bpc_pipe, &blocks_per_cu);
-      if (rc) return rc;
-      const int64_t cap = (int64_t)ctx->num_cus * blocks_per_cu;
-      const int64_t need4 = gficf_ceil_div(gficf_ceil_div(ce - cb, 4), C::WAVES);       // a wave takes four cells at a time
-      unsigned grid4 = (unsigned)(need4 < cap ? need4 : cap);
-      if (o.xcd && grid4 > 8) grid4 = (grid4 + 7u) & ~7u;       // (surplus workgroups find no cell and leave)
-      if (nob16)
-        hipLaunchKernelGGL((k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, !CMP, MAP>), dim3(grid4), dim3(C::WAVES * 64), lds_bytes, ctx->stream,
-                           table, N, k, cb, ce, o);
-      else
-        hipLaunchKernelGGL((k_jaccard_edges_pipe<KPAD, BIG, CMP, OUT, true, MAP>), dim3(grid4), dim3(C::WAVES * 64), lds_bytes, ctx->stream, table,
-                           N, k, cb, ce, o);
-      GFICF_HIP_CHECK(hipGetLastError());
-      return GFICF_OK;
+        return pipe(std::false_type{});
+      });
     }
   }
-  const int rc = edge_blocks_per_cu(k_jaccard_edges<KPAD, BIG, CMP, OUT, MAP>, C::WAVES * 64, lds_bytes, bpc_general, &blocks_per_cu);
-  if (rc) return rc;
-  const int64_t blocks_needed = gficf_ceil_div(ce - cb, C::WAVES);
-  const int64_t cap = (int64_t)ctx->num_cus * blocks_per_cu;
-  unsigned grid = (unsigned)(blocks_needed < cap ? blocks_needed : cap);
-  if (o.xcd && grid > 8) grid = (grid + 7u) & ~7u;
-  hipLaunchKernelGGL((k_jaccard_edges<KPAD, BIG, CMP, OUT, MAP>), dim3(grid), dim3(C::WAVES * 64), lds_bytes, ctx->stream, table,
-                     N, k, cb, ce, o);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
-}
-
-template <int KPAD, bool BIG, bool CMP, int OUT>
-int launch_edges_o(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  if constexpr (OUT != OUT_U16) {              // (the counts-only output has no neighbour column)
-    if (o.l2g) return launch_edges_m<KPAD, BIG, CMP, OUT, true>(ctx, table, N, k, cb, ce, o);
-  }
-  return launch_edges_m<KPAD, BIG, CMP, OUT, false>(ctx, table, N, k, cb, ce, o);
-}
-
-template <int KPAD, bool BIG, bool CMP>
-int launch_edges_t(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  if (o.u16) return launch_edges_o<KPAD, BIG, CMP, OUT_U16>(ctx, table, N, k, cb, ce, o);
-  if (o.u) return launch_edges_o<KPAD, BIG, CMP, OUT_RMAT_U>(ctx, table, N, k, cb, ce, o);
-  return launch_edges_o<KPAD, BIG, CMP, OUT_RMAT>(ctx, table, N, k, cb, ce, o);
+  return launch_resident<k_jaccard_edges<KPAD, BIG, CMP, OUT, MAP>>(ctx, C::WAVES * 64, lds_bytes, gficf_ceil_div(ce - cb, C::WAVES), o.xcd, table, N,
+                                                                   k, cb, ce, o);
 }
 
 // dual rows (32 < k <= 55, N <= 131070): the bit-set kernel
 template <int NST, int OUT, bool MAP>
-int launch_bits_m(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  static std::atomic<int> bpc{0};
+int launch_edges_bits(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, const EdgeOut& o) {
+  constexpr auto kernel = k_jaccard_edges_bits<NST, OUT, MAP>;
   static std::atomic<bool> attr_set[64];
   if (!attr_set[ctx->device & 63]) {
-    GFICF_HIP_CHECK(hipFuncSetAttribute((const void*)k_jaccard_edges_bits<NST, OUT, MAP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BITS_LDS_BYTES));
+    GFICF_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BITS_LDS_BYTES));
     attr_set[ctx->device & 63] = true;
   }
-  int blocks_per_cu = 1;
-  const int rc = edge_blocks_per_cu(k_jaccard_edges_bits<NST, OUT, MAP>, BITS_WAVES * 64, BITS_LDS_BYTES, bpc, &blocks_per_cu);
-  if (rc) return rc;
-  const int64_t need = gficf_ceil_div(ce - cb, BITS_WAVES);
-  const int64_t cap = (int64_t)ctx->num_cus * blocks_per_cu;
-  unsigned grid = (unsigned)(need < cap ? need : cap);
-  if (o.xcd && grid > 8) grid = (grid + 7u) & ~7u;
-  hipLaunchKernelGGL((k_jaccard_edges_bits<NST, OUT, MAP>), dim3(grid), dim3(BITS_WAVES * 64), BITS_LDS_BYTES, ctx->stream, table, N, k, cb, ce, o);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  return launch_resident<kernel>(ctx, BITS_WAVES * 64, BITS_LDS_BYTES, gficf_ceil_div(ce - cb, BITS_WAVES), o.xcd, table, N, k, cb, ce, o);
 }
 
-template <int NST>
-int launch_bits(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  if (o.u16) return launch_bits_m<NST, OUT_U16, false>(ctx, table, N, k, cb, ce, o);
-  if (o.u) return o.l2g ? launch_bits_m<NST, OUT_RMAT_U, true>(ctx, table, N, k, cb, ce, o) : launch_bits_m<NST, OUT_RMAT_U, false>(ctx, table, N, k, cb, ce, o);
-  return o.l2g ? launch_bits_m<NST, OUT_RMAT, true>(ctx, table, N, k, cb, ce, o) : launch_bits_m<NST, OUT_RMAT, false>(ctx, table, N, k, cb, ce, o);
-}
-
-template <int KPAD>
-int launch_edges(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  if constexpr (KPAD == 64) {
-    if (table_fmt(N, k).dual) {
-      const int nst = (k + 7) / 8;                           // gather steps of a cell, 8 neighbour rows each
-      return nst <= 5 ? launch_bits<5>(ctx, table, N, k, cb, ce, o) : nst == 6 ? launch_bits<6>(ctx, table, N, k, cb, ce, o)
-                                                                                : launch_bits<7>(ctx, table, N, k, cb, ce, o);
-    }
-  }
-  // 32-bit byte offsets and the 24-bit hash multiply need table < 4 GiB and ids < 2^24
-  static const bool force_big = getenv("GFICF_JACCARD_FORCE_BIG") != nullptr;   // test hook for the 64-bit variant
-  const bool big = force_big || N >= (1ll << 24) || N * (int64_t)KPAD * 4 >= (1ll << 32);
-  if (KPAD >= 32 && table_fmt(N, k).compact)          // compact rows: N < 2^17, never the 64-bit variant (the test hook switches them off)
-    return launch_edges_t<KPAD, false, KPAD >= 32>(ctx, table, N, k, cb, ce, o);
-  return big ? launch_edges_t<KPAD, true, false>(ctx, table, N, k, cb, ce, o)
-             : launch_edges_t<KPAD, false, false>(ctx, table, N, k, cb, ce, o);
-}
-
-int launch_edges_k(gficf_ctx* ctx, const uint32_t* t, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
+// The edge kernel of a table, top to bottom: sorted rows? dual rows? 64-bit offsets? then (KPAD, CMP) x (OUT, MAP) by the two tables
+// of jaccard_shared.h, and launch_edges_hash picks the pipelined or the general kernel.
+int launch_edges(gficf_ctx* ctx, const uint32_t* t, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
   if (sorted_fmt(k)) return launch_edges_sorted(ctx, t, N, k, cb, ce, o);      // exact for every row: no flags, no deferred report
   if (const char* e = getenv("GFICF_JACCARD_XCD")) o.xcd = atoi(e) != 0 ? 1u : 0u;     // A/B switch, read per call
   if (ctx->jaccard_assume_distinct) o.dup_status = ctx->d_status;                      // the table may carry no duplicate flags
-  switch (kpad_for(k)) {
-    case 16: return launch_edges<16>(ctx, t, N, k, cb, ce, o);
-    case 32: return launch_edges<32>(ctx, t, N, k, cb, ce, o);
-    case 64: return launch_edges<64>(ctx, t, N, k, cb, ce, o);
-    case 128: return launch_edges<128>(ctx, t, N, k, cb, ce, o);
-    default: return launch_edges<256>(ctx, t, N, k, cb, ce, o);
+  const TableFmt f = table_fmt(N, k);
+  if (f.dual) {
+    const int nst = (k + 7) / 8;                             // gather steps of a cell, 8 neighbour rows each
+    return with_edge_out(o, [&](auto OUT, auto MAP) {
+      return nst <= 5 ? launch_edges_bits<5, OUT, MAP>(ctx, t, N, k, cb, ce, o) : nst == 6 ? launch_edges_bits<6, OUT, MAP>(ctx, t, N, k, cb, ce, o)
+                                                                                          : launch_edges_bits<7, OUT, MAP>(ctx, t, N, k, cb, ce, o);
+    });
   }
+  // 32-bit byte offsets and the 24-bit hash multiply need table < 4 GiB and ids < 2^24
+  static const bool force_big = getenv("GFICF_JACCARD_FORCE_BIG") != nullptr;   // test hook for the 64-bit variant
+  const bool big = force_big || N >= (1ll << 24) || N * (int64_t)f.kpad * 4 >= (1ll << 32);
+  return with_table_fmt(f, [&](auto KPAD, auto CMP) {
+    return with_edge_out(o, [&](auto OUT, auto MAP) {
+      if constexpr (CMP)                       // compact rows: N < 2^17, never the 64-bit variant (the test hook switches them off)
+        return launch_edges_hash<KPAD, false, true, OUT, MAP>(ctx, t, N, k, cb, ce, o);
+      else
+        return with_flag(big, [&](auto BIG) { return launch_edges_hash<KPAD, BIG, false, OUT, MAP>(ctx, t, N, k, cb, ce, o); });
+    });
+  });
 }
 
 // edges from which gficf_jaccard_host returns through uint16 counts + a host-side expansion instead of copying the 24 B/edge matrix
@@ -535,7 +462,7 @@ int gficf_jaccard_edges_device(gficf_ctx* ctx, const int32_t* d_table, int64_t N
   if (cell_end == cell_begin || k == 0) return GFICF_OK;
   if (!d_table || !d_src || !d_dst || !d_w) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   EdgeOut o{d_src, d_dst, d_w, d_u, nullptr, 0};
-  return launch_edges_k(ctx, (const uint32_t*)d_table, N, k, cell_begin, cell_end, o);
+  return launch_edges(ctx, (const uint32_t*)d_table, N, k, cell_begin, cell_end, o);
 }
 
 /* Rows of a sharded sub-problem in local ids (halo.hip): n_ext rows, ids in [1, n_ext], 0 = no id in the slot. */
@@ -602,32 +529,17 @@ static int halo_ingest_launch(gficf_ctx* ctx, const int32_t* d_idx, int64_t n_lo
   // rows taken to hold distinct ids (gficf_ctx_set_jaccard_distinct): no duplicate scan here either — a rank's own rows are
   // inserted by its mapped edge kernel, which reports a repeated id; the halo rows are own rows of the ranks that sent them
   const bool scan = !ctx->jaccard_assume_distinct;
-#define LAUNCH_HALO_INGEST(KP, CM)                                                                                                \
-  do {                                                                                                                            \
-    if (scan)                                                                                                                     \
-      hipLaunchKernelGGL((k_ingest_tile<int32_t, KP, CM, true>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, row_end, k, ld, n_ext, \
-                         (uint32_t*)d_table, ctx->d_status, 1, hm);                                                               \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((k_ingest_tile<int32_t, KP, CM, true, false>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, row_end, k, ld, \
-                         n_ext, (uint32_t*)d_table, ctx->d_status, 1, hm);                                                        \
-  } while (0)
-  switch (f.kpad) {
-    case 16: LAUNCH_HALO_INGEST(16, false); break;
-    case 32: if (f.compact) LAUNCH_HALO_INGEST(32, true); else LAUNCH_HALO_INGEST(32, false); break;
-    default:
-      if (f.dual) {
-        if (scan)
-          hipLaunchKernelGGL((k_ingest_tile<int32_t, 64, true, true, true, true>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, row_end, k, ld, n_ext,
-                             (uint32_t*)d_table, ctx->d_status, 1, hm);
-        else
-          hipLaunchKernelGGL((k_ingest_tile<int32_t, 64, true, true, false, true>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, row_end, k, ld, n_ext,
-                             (uint32_t*)d_table, ctx->d_status, 1, hm);
-      } else if (f.compact) LAUNCH_HALO_INGEST(64, true); else LAUNCH_HALO_INGEST(64, false);
-      break;
-  }
-#undef LAUNCH_HALO_INGEST
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  auto tile = [&](auto KPAD, auto CMP, auto DUAL) {
+    return with_flag(scan, [&](auto SCAN) {
+      return launch_grid<k_ingest_tile<int32_t, KPAD, CMP, true, SCAN, DUAL>>(ctx, dim3(grid), dim3(256), 0, d_idx, row_end, k, ld, n_ext,
+                                                                           (uint32_t*)d_table, ctx->d_status, 1, hm);
+    });
+  };
+  if (f.dual) return tile(std::integral_constant<int, 64>{}, std::true_type{}, std::true_type{});
+  return with_table_fmt(f, [&](auto KPAD, auto CMP) {
+    if constexpr (KPAD <= 64) return tile(KPAD, CMP, std::false_type{});
+    else return (int)GFICF_ERR_UNSUPPORTED;                  // (not reached: k <= 64 was checked above)
+  });
 }
 
 int gficf_jaccard_halo_serve_ingest_device(gficf_ctx* ctx, const int32_t* d_idx, int64_t n_local, int k, int64_t ld, int64_t N_total,
@@ -668,7 +580,7 @@ int gficf_jaccard_edges_mapped_device(gficf_ctx* ctx, const int32_t* d_table, in
   if (n_cells == 0 || k == 0) return GFICF_OK;
   if (!d_table || !d_l2g || !d_src || !d_dst || !d_w) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   EdgeOut o{d_src, d_dst, d_w, d_u, nullptr, 0, d_l2g, (uint32_t)src_offset};
-  return launch_edges_k(ctx, (const uint32_t*)d_table, n_ext, k, 0, n_cells, o);
+  return launch_edges(ctx, (const uint32_t*)d_table, n_ext, k, 0, n_cells, o);
 }
 
 int gficf_jaccard_one_launch(gficf_ctx* ctx, int64_t N, int k) { return (ctx && direct_applies(ctx, N, k)) ? 1 : 0; }
@@ -798,7 +710,7 @@ static int gficf_jaccard_counts_host_body(gficf_ctx* ctx, const void* idx, int i
     if (direct_applies(ctx, N, k)) rc = launch_direct(ctx, d_idx, idx_is_f64, N, k, ld, o);      // small problem: one launch, no table
     else {
       rc = gficf_jaccard_ingest_device(ctx, d_idx, idx_is_f64, N, k, ld, N, d_table);
-      if (!rc) rc = launch_edges_k(ctx, (const uint32_t*)d_table, N, k, 0, N, o);
+      if (!rc) rc = launch_edges(ctx, (const uint32_t*)d_table, N, k, 0, N, o);
     }
     if (!rc) io.down(u, d_u, sizeof(uint16_t) * (size_t)E);
   }
@@ -916,7 +828,7 @@ static int edges_filtered(gficf_ctx* ctx, const int32_t* d_table, int64_t N, int
   // 1. intersection counts only (no 24 B/edge matrix)
   EdgeOut o{nullptr, nullptr, nullptr, nullptr, d_u_ws, set_mode};
   const uint32_t* t = (const uint32_t*)d_table;
-  rc = launch_edges_k(ctx, t, N, k, cell_begin, cell_end, o);
+  rc = launch_edges(ctx, t, N, k, cell_begin, cell_end, o);
   if (rc) return rc;
   // 2. kept edges per cell -> offsets
   hipLaunchKernelGGL(k_edge_kept_count, dim3((unsigned)gficf_ceil_div(n_cells, 256)), dim3(256), 0, ctx->stream, d_u_ws,
@@ -927,27 +839,14 @@ static int edges_filtered(gficf_ctx* ctx, const int32_t* d_table, int64_t N, int
   // 3. ordered compacted write
   int64_t blocks = gficf_ceil_div(n_cells, 4);
   if (blocks > (int64_t)ctx->num_cus * 8) blocks = (int64_t)ctx->num_cus * 8;
-  if (sorted_fmt(k)) {
-    hipLaunchKernelGGL(k_edge_write_sorted, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, t, d_u_ws, k, cell_begin, n_cells, d_cell_ptr, d_from,
-                       d_to, d_weight, sorted_kp(k), d_order);
-    GFICF_HIP_CHECK(hipGetLastError());
-    return GFICF_OK;
-  }
-#define LAUNCH_EW(KP, CM)                                                                                               \
-  hipLaunchKernelGGL((k_edge_write<KP, CM>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, t, d_u_ws, k, cell_begin, \
-                     n_cells, d_cell_ptr, d_from, d_to, d_weight, pitch, d_order)
-  const bool cm = table_fmt(N, k).compact;
-  const int pitch = table_fmt(N, k).row_words;
-  switch (kpad_for(k)) {
-    case 16: LAUNCH_EW(16, false); break;
-    case 32: if (cm) LAUNCH_EW(32, true); else LAUNCH_EW(32, false); break;
-    case 64: if (cm) LAUNCH_EW(64, true); else LAUNCH_EW(64, false); break;
-    case 128: if (cm) LAUNCH_EW(128, true); else LAUNCH_EW(128, false); break;
-    default: if (cm) LAUNCH_EW(256, true); else LAUNCH_EW(256, false); break;
-  }
-#undef LAUNCH_EW
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  if (sorted_fmt(k))
+    return launch_grid<k_edge_write_sorted>(ctx, dim3((unsigned)blocks), dim3(256), 0, t, d_u_ws, k, cell_begin, n_cells, d_cell_ptr, d_from, d_to,
+                                            d_weight, sorted_kp(k), d_order);
+  const TableFmt f = table_fmt(N, k);
+  return with_table_fmt(f, [&](auto KPAD, auto CMP) {
+    return launch_grid<k_edge_write<KPAD, CMP>>(ctx, dim3((unsigned)blocks), dim3(256), 0, t, d_u_ws, k, cell_begin, n_cells, d_cell_ptr, d_from, d_to,
+                                                d_weight, f.row_words, d_order);
+  });
 }
 
 int gficf_jaccard_edges_filtered_device(gficf_ctx* ctx, const int32_t* d_table, int64_t N, int k, int64_t cell_begin,

@@ -125,11 +125,9 @@ template <typename T, int KPAD>
 int launch_direct_t(gficf_ctx* ctx, const T* d_idx, int64_t N, int k, int64_t ld, EdgeOut o) {
   const int64_t need = gficf_ceil_div(N, 4), cap = (int64_t)ctx->num_cus * 8;
   const unsigned grid = (unsigned)(need < cap ? need : cap);
-  if (o.u16) hipLaunchKernelGGL((k_jaccard_direct<T, KPAD, OUT_U16>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, N, k, ld, o, ctx->d_status);
-  else if (o.u) hipLaunchKernelGGL((k_jaccard_direct<T, KPAD, OUT_RMAT_U>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, N, k, ld, o, ctx->d_status);
-  else hipLaunchKernelGGL((k_jaccard_direct<T, KPAD, OUT_RMAT>), dim3(grid), dim3(256), 0, ctx->stream, d_idx, N, k, ld, o, ctx->d_status);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
+  return with_edge_out(o, [&](auto OUT, auto) {        // (no mapped form: the neighbour column is the input's own ids)
+    return launch_grid<k_jaccard_direct<T, KPAD, OUT>>(ctx, dim3(grid), dim3(256), 0, d_idx, N, k, ld, o, ctx->d_status);
+  });
 }
 
 inline int launch_direct(gficf_ctx* ctx, const void* d_idx, int idx_is_f64, int64_t N, int k, int64_t ld, EdgeOut o) {

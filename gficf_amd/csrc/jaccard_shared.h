@@ -1,4 +1,5 @@
 // jaccard_shared.h — what the Jaccard kernels share: the table formats (one row per cell; a function of (N, k) and the GFICF_JACCARD_* switches),
+// the host's launch dispatch (with_table_fmt, with_edge_out, with_flag, launch_grid),
 // the edge kernels' configuration (JCfg), output descriptor (EdgeOut), set probes and the exact per-cell path (slow_cell).  Until round 6
 // this text sat in jaccard.hip between the #include lines of the kernel headers, which therefore compiled only inside that file, in that
 // order; now every kernel header includes this one and stands on its own (`hipcc -fsyntax-only -x hip <header>`: tests/test_abi.py).
@@ -135,6 +136,33 @@ inline TableFmt table_fmt(int64_t N_total, int k) {
   f.dual = f.compact && f.kpad == 64 && k <= 55 && N_total <= 131070 && dual_enabled();
   f.row_words = f.dual ? DUAL_PITCH : f.compact ? f.kpad / 2 : f.kpad;
   return f;
+}
+
+// ------------------------------------------------------------------------ launch dispatch (host)
+// A runtime value becomes a template argument by calling a generic lambda with a tag: fn(KPAD, CMP) below receives
+// std::integral_constant<int, ..> / std::bool_constant<..> objects, which convert to their value in a template argument list.
+// with_table_fmt is the ONE place that knows which (KPAD, CMP) pairs exist for hash-set rows: 16 slots are never compact.  What
+// selects another kernel, not another argument — dual rows, sorted rows, "register ingest up to 64 slots" — is an `if` of the caller.
+template <typename F>
+inline int with_flag(bool b, F&& fn) { return b ? fn(std::true_type{}) : fn(std::false_type{}); }
+
+template <typename F>
+inline int with_table_fmt(const TableFmt& f, F&& fn) {
+  switch (f.kpad) {
+    case 16: return fn(std::integral_constant<int, 16>{}, std::false_type{});
+    case 32: return with_flag(f.compact, [&](auto CMP) { return fn(std::integral_constant<int, 32>{}, CMP); });
+    case 64: return with_flag(f.compact, [&](auto CMP) { return fn(std::integral_constant<int, 64>{}, CMP); });
+    case 128: return with_flag(f.compact, [&](auto CMP) { return fn(std::integral_constant<int, 128>{}, CMP); });
+    default: return with_flag(f.compact, [&](auto CMP) { return fn(std::integral_constant<int, 256>{}, CMP); });
+  }
+}
+
+// one launch on the context's stream, and its error
+template <auto Kernel, typename... A>
+inline int launch_grid(gficf_ctx* ctx, dim3 grid, dim3 block, size_t lds_bytes, A... args) {
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, ctx->stream, args...);
+  GFICF_HIP_CHECK(hipGetLastError());
+  return GFICF_OK;
 }
 
 // id of slot j (0 = none) / duplicate flag of a row given as 32-bit words (global memory or LDS)
@@ -371,6 +399,14 @@ __device__ inline uint32_t xcd_block(uint32_t b, uint32_t nb, uint32_t on) {
 constexpr int OUT_RMAT = 0;       // the three columns of the reference's edge matrix
 constexpr int OUT_RMAT_U = 1;     // the same + int32 intersection counts
 constexpr int OUT_U16 = 2;        // uint16 intersection counts only (edge filter, compact host return)
+
+// fn(OUT, MAP) for what an EdgeOut asks for; MAP = the neighbour column goes through o.l2g (the counts-only output has no such column)
+template <typename F>
+inline int with_edge_out(const EdgeOut& o, F&& fn) {
+  if (o.u16) return fn(std::integral_constant<int, OUT_U16>{}, std::false_type{});
+  if (o.u) return with_flag(o.l2g != nullptr, [&](auto MAP) { return fn(std::integral_constant<int, OUT_RMAT_U>{}, MAP); });
+  return with_flag(o.l2g != nullptr, [&](auto MAP) { return fn(std::integral_constant<int, OUT_RMAT>{}, MAP); });
+}
 
 template <int OUT>
 __device__ inline void store_edge(const EdgeOut o, int64_t r, int64_t cell, uint32_t dst, int u,

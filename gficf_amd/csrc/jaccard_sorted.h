@@ -227,30 +227,16 @@ int launch_ingest_sorted(gficf_ctx* ctx, const T* d_idx, int64_t n_rows, int k, 
   return GFICF_OK;
 }
 
-template <int OUT>
-int launch_edges_sorted_o(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
+inline int launch_edges_sorted(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
   const int kp = sorted_kp(k);
   const int use_lds = kp <= SORTED_EDGE_LDS_KP ? 1 : 0;
   const size_t lds = use_lds ? sizeof(uint32_t) * 6 * (size_t)kp : 0;
   const int64_t cap = (int64_t)ctx->num_cus * (use_lds ? (lds > 32768 ? 1 : lds > 16384 ? 2 : 4) : 8);
   const int64_t cells = ce - cb;
   const unsigned grid = (unsigned)(cells < cap ? cells : cap);
-  if constexpr (OUT != OUT_U16) {
-    if (o.l2g) {
-      hipLaunchKernelGGL((k_jaccard_edges_sorted<OUT, true>), dim3(grid), dim3(256), lds, ctx->stream, table, N, k, cb, ce, o, kp, use_lds);
-      GFICF_HIP_CHECK(hipGetLastError());
-      return GFICF_OK;
-    }
-  }
-  hipLaunchKernelGGL((k_jaccard_edges_sorted<OUT, false>), dim3(grid), dim3(256), lds, ctx->stream, table, N, k, cb, ce, o, kp, use_lds);
-  GFICF_HIP_CHECK(hipGetLastError());
-  return GFICF_OK;
-}
-
-inline int launch_edges_sorted(gficf_ctx* ctx, const uint32_t* table, int64_t N, int k, int64_t cb, int64_t ce, EdgeOut o) {
-  if (o.u16) return launch_edges_sorted_o<OUT_U16>(ctx, table, N, k, cb, ce, o);
-  if (o.u) return launch_edges_sorted_o<OUT_RMAT_U>(ctx, table, N, k, cb, ce, o);
-  return launch_edges_sorted_o<OUT_RMAT>(ctx, table, N, k, cb, ce, o);
+  return with_edge_out(o, [&](auto OUT, auto MAP) {
+    return launch_grid<k_jaccard_edges_sorted<OUT, MAP>>(ctx, dim3(grid), dim3(256), lds, table, N, k, cb, ce, o, kp, use_lds);
+  });
 }
 
 }  // namespace

@@ -322,6 +322,35 @@ def test_wide_rows_for_small_data_sets_match(tmp_path):
         assert r.returncode == 0 and "ok" in r.stdout, (compact, r.stderr[-2000:])
 
 
+@pytest.mark.parametrize("hook", ["GFICF_JACCARD_NO_PIPE=1", "GFICF_JACCARD_INGEST_REG=1", "GFICF_JACCARD_XCD=0",
+                                  "GFICF_JACCARD_BLOCKS_PER_CU=3"])
+def test_launch_hooks_reach_the_same_bits(hook):
+    """Branches of the launch dispatch that only a hook reaches: the general edge kernel at k <= 64, the register ingest,
+    the grid that is not renumbered by XCD, an overridden occupancy.  A fresh process per setting (the hooks are read once).
+    Shapes: either side of the 16/32 and 32/64 pads, dual rows ((700, 33), (3000, 50)), ids with bit 16 ((70000, 30): the
+    kernel variant that looks for it); one row repeats an id, so that the exact re-run is dispatched too."""
+    import subprocess
+    import sys
+
+    code = (
+        "import numpy as np, gficf_amd, oracle\n"
+        "from gficf_amd import synth\n"
+        "for N, k in ((1000, 15), (1000, 16), (999, 32), (700, 33), (3000, 50), (70000, 30)):\n"
+        "    mat = synth.knn_windowed(N, k, W=max(100, k), seed=N)\n"
+        "    mat[5, 2] = mat[5, 0]\n"
+        "    want = oracle.jaccard(mat, nthreads=4)[0]\n"
+        "    assert np.array_equal(gficf_amd.rcpp_parallel_jaccard_coef(mat, False), want), (N, k)\n"
+        "    ed = gficf_amd.jaccard_edges(np.concatenate([np.arange(1, N + 1, dtype=mat.dtype)[:, None], mat], axis=1))\n"
+        "    kp = want[:, 2] > 0\n"
+        "    assert np.array_equal(ed['from'], want[kp, 0]) and np.array_equal(ed['to'], want[kp, 1]) and np.array_equal(ed['weight'], want[kp, 2]), (N, k)\n"
+        "print('ok')\n")
+    name, value = hook.split("=")
+    env = dict(os.environ, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    env[name] = value
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ok" in r.stdout, (hook, r.stderr[-2000:])
+
+
 def test_config3_shape_54k_cells_k30_bit_exact(ops):
     """BASELINE config 3 (Tabula-Muris-sized: ~54 k cells, k = 30 Phenograph graph): whole edge matrix and
     intersection counts bit-exact vs the oracle, through the device pipeline and through the host C ABI."""
