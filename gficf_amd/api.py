@@ -1730,6 +1730,62 @@ def rsvd(A_csc_genes_x_cells, k: int, p: int = 10, q: int = 2, seed: int = 18058
     return {"d": d, "u": u, "v": genes, "cells": cells, "centre": mu}
 
 
+# ------------------------------------------------------------------ exact truncated SVD (libgficf_svds.so)
+SVDS_MAX_B = 32
+SVDS_MAX_M = 128
+
+
+def svds(A_csc_genes_x_cells, k: int, centre: bool = False, tol: float = 1e-10, block: int = 8, m: int | None = None,
+         max_cycles: int = 1000, seed: int = 180582, start=None, ctx: Context | None = None) -> dict:
+    """``RSpectra::svds(t(M), k)`` for the genes x cells matrix ``M`` (scipy CSC): the k largest singular triplets of the cells x
+    genes matrix ``A = t(M)``, with ``centre`` of ``A`` minus its column means (never densified), to the accuracy of f64 and
+    independent of any random sketch.  The contract is the method of include/gficf_svds.h — block Lanczos with full
+    reorthogonalisation and thick restart on the short side, n = min(N, G) — not RSpectra's bits: ``block`` is the block width
+    b (at most 32, and at most ``m``), ``m`` the basis capacity (default min(n, 128); k + 2 b <= m unless m = n), ``tol``
+    RSpectra's default.  The start block (n x b) is drawn here, ``np.random.default_rng(seed).standard_normal``, unless given;
+    the library holds no generator, and the converged result does not depend on it beyond rounding.
+
+    Returns :func:`rsvd`'s keys (``d``, ``u``, ``v``, ``cells``, ``centre``) plus ``residuals`` (k values
+    ``||C v - theta v|| / theta`` as the iteration estimates them), ``converged`` (how many of the k pairs met ``tol``),
+    ``cycles``, ``products`` (applications of the operator, two sparse products each) and ``exhausted`` (the Krylov space
+    filled the whole space or closed: the result is then exact whatever ``converged`` says).  ``converged < k`` without
+    exhaustion gives a warning naming the count, as RSpectra does, never an exception.  An eigenvalue of multiplicity above
+    b is returned at most b times."""
+    from . import _svds_lib
+
+    M, colptr, rowidx, x = _csc_parts(A_csc_genes_x_cells)
+    G, N = M.shape
+    k, n = int(k), min(G, N)
+    m = min(n, SVDS_MAX_M) if m is None else int(m)
+    if start is None:
+        start = np.random.default_rng(seed).standard_normal((n, max(1, min(int(block), m))))
+    start = np.asfortranarray(start, dtype=np.float64)
+    if start.ndim != 2 or start.shape[0] != n:
+        raise ValueError(f"start must have min(N, G) = {n} rows")
+    b = start.shape[1]
+    kk = max(k, 1)
+    d = np.zeros(kk, dtype=np.float64)
+    cells = np.zeros((kk, N), dtype=np.float64)               # C-order (k, N) == column-major N x k
+    genes = np.zeros((kk, G), dtype=np.float64)
+    resid = np.zeros(kk, dtype=np.float64)
+    info = np.zeros(4, dtype=np.int64)
+    mu = np.zeros(G, dtype=np.float64) if centre else None
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_svds_lib.load().gficf_svds_host(ctx.handle, G, N, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), 1 if centre else 0,
+                                           _np_ptr(start), k, b, m, float(tol), int(max_cycles), _np_ptr(d), _np_ptr(cells), _np_ptr(genes),
+                                           _np_ptr(mu), _np_ptr(resid), _np_ptr(info)))
+    cells, genes = cells.T, genes.T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = np.where(d > 0, cells / d, 0.0)
+    converged, exhausted = int(info[2]), bool(info[3])
+    if converged < k and not exhausted:
+        warnings.warn(f"svds: only {converged} of the {k} singular values converged to tol = {tol:g} in {int(info[0])} cycles; "
+                      "raise max_cycles or m, or see residuals", stacklevel=2)
+    return {"d": d, "u": u, "v": genes, "cells": cells, "centre": mu, "residuals": resid, "converged": converged,
+            "cycles": int(info[0]), "products": int(info[1]), "exhausted": exhausted}
+
+
 # ------------------------------------------------------------------ overdispersed genes (libgficf_od.so)
 _OD_COLUMNS = ("v", "fit", "res", "lp", "lpa", "qv", "gsf")
 _RAW_ABSENT = "Raw Counts absent! Please run gficf normalization with storeRaw = T"
@@ -1969,9 +2025,30 @@ def _pca_unsupported(var_scale, use_odgenes, randomized):
         raise NotImplementedError("use_odgenes / var_scale need findOverDispersed (the mgcv::gam fit of the reference), which is not "
                                   "provided on mgcv's default thin-plate basis: pass use_odgenes=\"cr\" / var_scale=\"cr\" for the same model "
                                   "on its cubic regression spline (include/gficf_od.h), or use_odgenes=False and var_scale=False")
+    _pca_randomized(randomized)
+
+
+def _pca_randomized(randomized):
+    """``True`` (the randomized SVD, :func:`rsvd`) or ``"svds"`` (the exact one, :func:`svds`).  ``False`` stands for the
+    reference's RSpectra::svds / prcomp, whose bits are not provided: the exact decomposition has its own spelling, as
+    ``hvg="locfit"`` and ``var_scale="cr"`` have."""
+    if isinstance(randomized, str):
+        if randomized != "svds":
+            raise ValueError('randomized must be True or "svds"')
+        return "svds"
     if not randomized:
         raise NotImplementedError("randomized=False is the reference's full decomposition (RSpectra::svds / prcomp), which is not "
-                                  "provided: pass randomized=True")
+                                  'provided: pass randomized=True, or randomized="svds" for the exact truncated SVD of '
+                                  "include/gficf_svds.h")
+    return True
+
+
+def _pca_decompose(M, k, randomized, seed, centre, ctx):
+    """(the decomposition, what ``data["pca"]`` also stores about it): :func:`rsvd`, or :func:`svds` for ``randomized="svds"``."""
+    if _pca_randomized(randomized) == "svds":
+        r = svds(M, k, centre=centre, seed=seed, ctx=ctx)
+        return r, {"svds": {"converged": r["converged"], "residuals": r["residuals"], "cycles": r["cycles"]}}
+    return rsvd(M, k, seed=seed, centre=centre, ctx=ctx), {}
 
 
 def _pca_matrix(data: dict, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx):
@@ -2001,6 +2078,10 @@ def runPCA(data: dict, dim=None, var_scale=False, centre: bool = False, randomiz
     "centre": centre, "rescale": var_scale}`` plus ``"mean"``, the gene means that were subtracted (None without ``centre``; the
     reference's centring densifies and keeps nothing for later), and ``data["dimPCA"] = dim``.
 
+    ``randomized="svds"`` runs the exact truncated SVD instead (:func:`svds`: no sketch, no dependence on a test matrix) and
+    adds ``data["pca"]["svds"] = {"converged", "residuals", "cycles"}``; ``randomized=False``, the reference's spelling of
+    RSpectra::svds / prcomp, is refused.
+
     ``use_odgenes="cr"`` decomposes only the overdispersed genes of :func:`findOverDispersed` (:func:`odgenes_rows`, in
     ascending row order: where the reference decomposes in ``order(lp)`` order the result is a permutation of the same
     columns), ``var_scale="cr"`` scales every gene by its ``gsf`` first; either alone or both (:func:`select_scale_rows`).
@@ -2012,9 +2093,10 @@ def runPCA(data: dict, dim=None, var_scale=False, centre: bool = False, randomiz
     dim = _pca_dim(data, dim)
     _pca_unsupported(var_scale, use_odgenes, randomized)
     M, extra = _pca_matrix(data, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx)
-    r = rsvd(M, dim, seed=seed, centre=bool(centre), ctx=ctx)
+    r, how = _pca_decompose(M, dim, randomized, seed, bool(centre), ctx)
     data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": bool(centre), "rescale": bool(var_scale), "mean": r["centre"]}
     data["pca"].update(extra)
+    data["pca"].update(how)
     return data
 
 
@@ -2022,15 +2104,16 @@ def runLSA(data: dict, dim=None, var_scale=False, centre: bool = False, randomiz
            use_odgenes=False, n_odgenes=None, plot_odgenes: bool = False, ctx: Context | None = None) -> dict:
     """``runLSA(...)`` of the reference (R/dimensinalityReduction.R:19-65): ``rsvd::rsvd(t(data$gficf), k = dim)``, then
     ``cells = u %*% diag(d)`` and ``genes = v``.  As in the reference ``centre`` is accepted and not used
-    (``data$pca$centre <- F``, :59).  ``use_odgenes="cr"`` / ``var_scale="cr"``: as in :func:`runPCA`."""
+    (``data$pca$centre <- F``, :59).  ``use_odgenes="cr"`` / ``var_scale="cr"`` / ``randomized="svds"``: as in :func:`runPCA`."""
     if use_odgenes and data.get("rawCounts") is None:
         raise ValueError(_RAW_ABSENT)
     dim = _pca_dim(data, dim)
     _pca_unsupported(var_scale, use_odgenes, randomized)
     M, extra = _pca_matrix(data, var_scale, use_odgenes, n_odgenes, plot_odgenes, ctx)
-    r = rsvd(M, dim, seed=seed, centre=False, ctx=ctx)
+    r, how = _pca_decompose(M, dim, randomized, seed, False, ctx)
     data["pca"] = {"cells": r["cells"], "genes": r["v"], "centre": False, "rescale": bool(var_scale), "mean": None}
     data["pca"].update(extra)
+    data["pca"].update(how)
     return data
 
 
@@ -2056,15 +2139,15 @@ def computePCADim(data: dict, randomized: bool = True, subsampling: bool = False
     """``computePCADim(data, randomized, subsampling, plot)`` of the reference (R/dimensinalityReduction.R:206-230):
     ``rsvd(t(data$gficf), k = min(50, N))`` and the elbow rule (:func:`pca_dim_rule`) on its ``d``; ``data["dimPCA"]`` is set
     and the reference's line printed.  ``subsampling``: 5 % of the cells, drawn with numpy's generator from ``seed`` (the
-    reference uses R's ``sample``).  Raises where the reference would store NA."""
-    if not randomized:
-        raise NotImplementedError("randomized=False is RSpectra::svds, which is not provided: pass randomized=True")
+    reference uses R's ``sample``).  ``randomized="svds"``: the rule on the exact values (:func:`svds`).  Raises where the
+    reference would store NA."""
+    _pca_randomized(randomized)
     M = data["gficf"]
     N = M.shape[1]
     if subsampling:
         pick = np.random.default_rng(seed).choice(N, size=int(round(N / 100 * 5)), replace=False)
         M = M[:, pick]
-    d = rsvd(M, min(50, M.shape[1]), seed=seed, ctx=ctx)["d"]
+    d = _pca_decompose(M, min(50, M.shape[1]), randomized, seed, False, ctx)[0]["d"]
     if plot:
         try:
             import matplotlib.pyplot as plt
@@ -3698,6 +3781,31 @@ class HipOps:
         from . import _pca_lib
 
         check(_pca_lib.load().gficf_rsvd_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def svds_workspace_bytes(G: int, N: int, nnz: int, k: int, b: int, m: int) -> int:
+        """Device scratch of ``svds`` (libgficf_svds.so); 0 on arguments it would refuse."""
+        from . import _svds_lib
+
+        return int(_svds_lib.load().gficf_svds_workspace_bytes(int(G), int(N), int(nnz), int(k), int(b), int(m)))
+
+    def svds(self, G, n_cells, colptr, rowidx, x, centre, start, k, b, m, tol, max_cycles, ws, d, cells, genes, residuals, info, mean=None):
+        """Exact truncated SVD on device-resident tensors (colptr int64, rowidx int32, x float64: the genes x cells CSC matrix;
+        start: (b, min(N, G)) float64 == column-major min(N, G) x b; ws uint8 of ``svds_workspace_bytes``); d: k, cells: (k, N),
+        genes: (k, G), residuals: k, mean: G (with ``centre``) float64, info: 4 int64 (cycles, products, n_converged,
+        exhausted).  Reads 5 integers back per restart cycle and only enqueues otherwise: call ``svds_sync(ws)`` to wait and to
+        collect the deferred input errors."""
+        from . import _svds_lib
+
+        check(_svds_lib.load().gficf_svds_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x), int(rowidx.numel()),
+                                                 1 if centre else 0, _tptr(start), int(k), int(b), int(m), float(tol), int(max_cycles), _tptr(ws),
+                                                 int(ws.numel() * ws.element_size()), _tptr(d), _tptr(cells), _tptr(genes), _tptr(mean),
+                                                 _tptr(residuals), _tptr(info)))
+
+    def svds_sync(self, ws):
+        from . import _svds_lib
+
+        check(_svds_lib.load().gficf_svds_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def csc_tmm_workspace_bytes(nrows: int, ncols: int, nnz: int, l: int) -> int:
