@@ -16,15 +16,21 @@
 //                    of a remainder discarded), capped by N - 1 the last block is as narrow as what is left; G_last = W_last' W_last
 //   per restart      k_sp_rotate (V <- V Z, over the me columns of the cycle; Z: the kept Ritz vectors, chosen on the host), k_sp_apply<b> (the residual block W_last Z_last)
 //   at the end       k_sp_rotate, k_sp_amax_part / k_sp_sign_fin / k_sp_flip (the sign rule), k_sp_scale, k_sp_mul<b>, k_sp_resid<b>, the norms
+// The solve is one SpRun, its steps named after the rows above: prepare (once), start, then per cycle grow, read_cycle (the cycle's
+// one synchronisation), ritz, finish (at the end: when the estimate passes or nothing is left to restart with), else restart;
+// sp_solve is that loop.  What the host computes between a read-back and the next upload (Rayleigh-Ritz by cyclic Jacobi, the
+// estimate, the final rotation, which Ritz vectors a restart keeps) is spectral_ritz.h: no GPU header, tested on the CPU.
 // What bounds a block step at 54 000 vertices: P (12 B an entry) and V (N x m f64) both stay in the L2 / the infinity cache, the
 // kernels are short, so the step is about thirteen launch latencies.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "addon_status.h"
 #include "common.h"
 #include "gficf_spectral.h"
+#include "spectral_ritz.h"
 
 namespace {
 
@@ -439,17 +445,20 @@ __global__ __launch_bounds__(256) void k_sp_resid(double* __restrict__ W, const 
   for (int c = 0; c < B; ++c) W[r * B + c] -= theta[c] * X[r * B + c];
 }
 
-#define SP_DISPATCH(b, K, grid, ...)                                                             \
-  switch (b) {                                                                                   \
-    case 1: hipLaunchKernelGGL(K<1>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 2: hipLaunchKernelGGL(K<2>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 3: hipLaunchKernelGGL(K<3>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 4: hipLaunchKernelGGL(K<4>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 5: hipLaunchKernelGGL(K<5>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 6: hipLaunchKernelGGL(K<6>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 7: hipLaunchKernelGGL(K<7>, grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-    default: hipLaunchKernelGGL(K<8>, grid, dim3(256), 0, st, __VA_ARGS__); break;               \
+// the one place that knows for which block widths the templated kernels exist: fn(std::integral_constant<int, B>{}), default: 8
+template <typename F>
+void with_block_width(int b, F&& fn) {
+  switch (b) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    default: return fn(std::integral_constant<int, 8>{});
   }
+}
 
 // ------------------------------------------------------------------------------------------------ solve: workspace
 struct SpWs {
@@ -513,227 +522,214 @@ int sp_check(int64_t N, int64_t cap, int ndim, double tol, int m, int max_restar
   return GFICF_OK;
 }
 
-// eigen-decomposition of the symmetric n x n matrix A (row-major, destroyed): cyclic Jacobi, rows and columns swept in a fixed
-// order.  ev: the eigenvalues in DESCENDING order, Z (n x n row-major): column l the vector of ev[l].
-void sp_jacobi(std::vector<double>& A, int n, std::vector<double>& ev, std::vector<double>& Z) {
-  std::vector<double> Q((size_t)n * n, 0.0);
-  for (int i = 0; i < n; ++i) Q[(size_t)i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    double off = 0.0, diag = 0.0;
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < n; ++j) (i == j ? diag : off) += A[(size_t)i * n + j] * A[(size_t)i * n + j];
-    if (off <= 1e-32 * diag || off == 0.0) break;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = A[(size_t)p * n + q];
-        if (apq == 0.0) continue;
-        const double tau = (A[(size_t)q * n + q] - A[(size_t)p * n + p]) / (2.0 * apq);
-        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
-        const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
-        for (int k = 0; k < n; ++k) {
-          const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-          A[(size_t)k * n + p] = c * akp - s * akq;
-          A[(size_t)k * n + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-          A[(size_t)p * n + k] = c * apk - s * aqk;
-          A[(size_t)q * n + k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double qkp = Q[(size_t)k * n + p], qkq = Q[(size_t)k * n + q];
-          Q[(size_t)k * n + p] = c * qkp - s * qkq;
-          Q[(size_t)k * n + q] = s * qkp + c * qkq;
-        }
-      }
-  }
-  std::vector<int> order((size_t)n);
-  for (int i = 0; i < n; ++i) order[(size_t)i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return A[(size_t)x * n + x] > A[(size_t)y * n + y]; });
-  ev.assign((size_t)n, 0.0);
-  Z.assign((size_t)n * n, 0.0);
-  for (int l = 0; l < n; ++l) {
-    ev[(size_t)l] = A[(size_t)order[(size_t)l] * n + order[(size_t)l]];
-    for (int k = 0; k < n; ++k) Z[(size_t)k * n + l] = Q[(size_t)k * n + order[(size_t)l]];
-  }
+// a caller's workspace carved: carve(base) takes the pieces from base on and returns their total; base == nullptr only counts
+template <typename F>
+int sp_take(void* ws, size_t ws_bytes, F&& carve) {
+  const size_t need = carve((char*)nullptr);
+  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_CAPACITY, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  carve((char*)ws);
+  return GFICF_OK;
 }
 
-// the solve on a carved workspace, one component known.  Synchronises once per cycle.
-int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, int b, const double* d_start,
-             double tol, int m, int max_restarts, double* d_theta, double* d_resid, double* d_X, int64_t* h_info) {
-  hipStream_t st = ctx->stream;
-  const int mc = (int64_t)m < N - 1 ? m : (int)(N - 1), ldv = m, ldh = w.ldh;
-  const bool capped = (int64_t)mc < N - 1;                      // by m, not by the complement of q0
-  const dim3 rows(sp_grid(N)), one(1), red(SP_RED);
-  const size_t blk = sizeof(double) * (size_t)N * (size_t)b;
-  const double eps23 = std::pow(2.0, -52.0 * 2.0 / 3.0);
-  GFICF_HIP_CHECK(hipMemsetAsync(w.cc.status, 0, sizeof(uint32_t), st));
-  GFICF_HIP_CHECK(hipMemsetAsync(w.nhubs, 0, sizeof(uint32_t), st));
-  GFICF_HIP_CHECK(hipMemsetAsync(w.H, 0, sizeof(double) * (size_t)ldh * (size_t)(m + SP_MAXB), st));
-  hipLaunchKernelGGL(k_sp_degree, rows, dim3(256), 0, st, d_rowptr, d_val, N, w.q0, w.dis, w.cc.status);
-  hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.q0, 1, 1, (const double*)nullptr, (const double*)w.q0, 1, N, w.parts);
-  hipLaunchKernelGGL(k_sp_q0, rows, dim3(256), 0, st, (const double*)w.parts, N, w.q0);
-  hipLaunchKernelGGL(k_sp_hubs, rows, dim3(256), 0, st, d_rowptr, N, w.hubs, w.hub_cap, w.nhubs);
-  GFICF_HIP_CHECK(hipGetLastError());
+// ------------------------------------------------------------------------------------------------ solve: the run
+// One solve on a carved workspace, one component known; sp_solve below drives its steps.  The host mathematics between a cycle's
+// read-back and the next upload is spectral_ritz.h's.  What an asynchronous upload reads (rz.theta, zb, rs.up, rs.zl) lives here
+// and is written only right behind a synchronisation: untouched until the next one.
+struct SpRun {
+  gficf_ctx* ctx;
+  hipStream_t st;
+  SpWs w;
+  int64_t N;
+  int b, m, mc, ldv, ldh, max_restarts;
+  bool capped;                                                  // by m, not by the complement of q0
+  double tol;
   SpMul L;
-  L.N = N; L.rowptr = d_rowptr; L.col = d_col; L.val = d_val; L.dis = w.dis; L.hubs = w.hubs; L.nhubs = w.nhubs; L.hub_cap = w.hub_cap;
-  const unsigned vb = (unsigned)gficf_ceil_div(N, 256 / SP_GROUP);
-  const int64_t hw = w.hub_cap < (uint32_t)SP_HUB_WAVES ? (int64_t)w.hub_cap : (int64_t)SP_HUB_WAVES;
-  const dim3 mulgrid(vb + (unsigned)gficf_ceil_div(hw, 4));
+  unsigned vb;                                                  // the multiply's grid: vb blocks of vertices, then the waves of the hub list
+  dim3 mulgrid, rows, one{1}, red{SP_RED};
+  double *V, *Vo;                                               // the basis, and where a restart rotates it to
   int64_t mults = 0;
-  double *V = w.Va, *Vo = w.Vb;
-  auto mul = [&](const double* Xs, double* W) {
-    SP_DISPATCH(b, k_sp_mul, mulgrid, L, vb, Xs, W);
+  int restarts = 0, converged = 0;
+  int c0 = 0, bw = 0, nc = 0, keep = 0;                         // the last block's first column and width, the columns so far, the kept ones
+  std::vector<double> hH, hG, hres, zb, resid;                  // read back: H, G_last, the residual Gram matrix; Z[:, :b]; the residual norms
+  std::vector<int32_t> hflags;
+  SpRitz rz;
+  SpRestart rs;
+
+  SpRun(gficf_ctx* c, const SpWs& ws, int64_t n, const int64_t* rowptr, const int32_t* col, const float* val, int b_, double tol_, int m_, int mr)
+      : ctx(c), st(c->stream), w(ws), N(n), b(b_), m(m_), mc((int64_t)m_ < n - 1 ? m_ : (int)(n - 1)), ldv(m_), ldh(ws.ldh), max_restarts(mr),
+        capped((int64_t)mc < n - 1), tol(tol_), L{n, rowptr, col, val, ws.dis, ws.hubs, ws.nhubs, ws.hub_cap},
+        vb((unsigned)gficf_ceil_div(n, 256 / SP_GROUP)), rows(sp_grid(n)), V(ws.Va), Vo(ws.Vb), hH((size_t)ldh * (size_t)m_), hG((size_t)b_ * b_),
+        hres((size_t)b_ * b_), resid((size_t)b_, 0.0), hflags((size_t)m_) {
+    const int64_t hw = w.hub_cap < (uint32_t)SP_HUB_WAVES ? (int64_t)w.hub_cap : (int64_t)SP_HUB_WAVES;
+    mulgrid = dim3(vb + (unsigned)gficf_ceil_div(hw, 4));
+  }
+
+  // the degrees, q0 = sqrt(d) / |sqrt(d)|, the hub list
+  int prepare() {
+    GFICF_HIP_CHECK(hipMemsetAsync(w.cc.status, 0, sizeof(uint32_t), st));
+    GFICF_HIP_CHECK(hipMemsetAsync(w.nhubs, 0, sizeof(uint32_t), st));
+    GFICF_HIP_CHECK(hipMemsetAsync(w.H, 0, sizeof(double) * (size_t)ldh * (size_t)(m + SP_MAXB), st));
+    hipLaunchKernelGGL(k_sp_degree, rows, dim3(256), 0, st, L.rowptr, L.val, N, w.q0, w.dis, w.cc.status);
+    hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.q0, 1, 1, (const double*)nullptr, (const double*)w.q0, 1, N, w.parts);
+    hipLaunchKernelGGL(k_sp_q0, rows, dim3(256), 0, st, (const double*)w.parts, N, w.q0);
+    hipLaunchKernelGGL(k_sp_hubs, rows, dim3(256), 0, st, L.rowptr, N, w.hubs, w.hub_cap, w.nhubs);
+    GFICF_HIP_CHECK(hipGetLastError());
+    return GFICF_OK;
+  }
+
+  void mul(const double* Xs, double* W) {
+    with_block_width(b, [&](auto B) { hipLaunchKernelGGL(k_sp_mul<decltype(B)::value>, mulgrid, dim3(256), 0, st, L, vb, Xs, W); });
     ++mults;
-  };
-  // W against q0 and the first nc columns of V, twice; hcol >= 0: the coefficients are columns hcol .. of H
-  auto project = [&](int nc, int hcol) {
+  }
+  // W against q0 and the first na columns of V, twice; hcol >= 0: the coefficients are columns hcol .. of H
+  void project(int na, int hcol) {
     for (int pass = 0; pass < 2; ++pass) {
-      hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)V, ldv, nc, (const double*)w.q0, (const double*)w.W, b, N, w.parts);
-      hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, (nc + 1) * b, w.C,
-                         hcol >= 0 ? w.H + (size_t)ldh * (size_t)hcol : (double*)nullptr, ldh, nc, b, w.nb, pass);
-      SP_DISPATCH(b, k_sp_axpy, rows, (const double*)V, ldv, nc, (const double*)w.q0, (const double*)w.C, w.W, N);
+      hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)V, ldv, na, (const double*)w.q0, (const double*)w.W, b, N, w.parts);
+      hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, (na + 1) * b, w.C,
+                         hcol >= 0 ? w.H + (size_t)ldh * (size_t)hcol : (double*)nullptr, ldh, na, b, w.nb, pass);
+      with_block_width(b, [&](auto B) {
+        hipLaunchKernelGGL(k_sp_axpy<decltype(B)::value>, rows, dim3(256), 0, st, (const double*)V, ldv, na, (const double*)w.q0, (const double*)w.C, w.W, N);
+      });
     }
-  };
-  // W orthonormalised within itself, twice; its first bw columns become columns col0 .. of V
-  auto orth = [&](int col0, int bw) {
+  }
+  // W orthonormalised within itself, twice; its first width columns become columns col0 .. of V
+  void orth(int col0, int width) {
     for (int pass = 0; pass < 2; ++pass) {
-      hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.W, b, b, (const double*)nullptr, (const double*)w.W, b, N, w.parts);
-      hipLaunchKernelGGL(k_sp_chol, one, dim3(64), 0, st, (const double*)w.parts, b, bw, pass == 0 ? 1 : 0, (const double*)w.nb, w.T,
+      gram_parts(w.W);
+      hipLaunchKernelGGL(k_sp_chol, one, dim3(64), 0, st, (const double*)w.parts, b, width, pass == 0 ? 1 : 0, (const double*)w.nb, w.T,
                          pass == 1 ? w.flags + col0 : (int32_t*)nullptr);
-      SP_DISPATCH(b, k_sp_apply, rows, w.W, (const double*)w.T, N, pass == 1 ? V : (double*)nullptr, ldv, col0, bw, w.Xs, (const double*)w.dis);
+      with_block_width(b, [&](auto B) {
+        hipLaunchKernelGGL(k_sp_apply<decltype(B)::value>, rows, dim3(256), 0, st, w.W, (const double*)w.T, N, pass == 1 ? V : (double*)nullptr, ldv, col0,
+                           width, w.Xs, (const double*)w.dis);
+      });
     }
-  };
-  // the start block
-  GFICF_HIP_CHECK(hipMemcpyAsync(w.W, d_start, blk, hipMemcpyDeviceToDevice, st));
-  project(0, -1);
-  int bw = b < mc ? b : mc, c0 = 0, nc = bw, keep = 0, restarts = 0, converged = 0;
-  orth(0, bw);
-  GFICF_HIP_CHECK(hipGetLastError());
-  std::vector<double> hH((size_t)ldh * (size_t)m), hG((size_t)b * b), kept, ev, Z, A, Zfull, up, zl, hres((size_t)b * b);
-  std::vector<int32_t> hflags((size_t)m);
-  std::vector<double> theta((size_t)b, 0.0), resid((size_t)b, 0.0);
-  for (;;) {
-    // ---- one cycle: the basis grown to mc columns (capped by m: to its last full block), then the remainder of the last block and its Gram matrix
+  }
+  // the chunks of X' X (b x b) into parts; gram: added in order into G
+  void gram_parts(const double* X) {
+    hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, X, b, b, (const double*)nullptr, X, b, N, w.parts);
+  }
+  void gram(const double* X) {
+    gram_parts(X);
+    hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, b * b, w.G, (double*)nullptr, 0, 0, b, (double*)nullptr, 0);
+  }
+
+  // the start block: projected, orthonormalised, the first columns of V
+  int start(const double* d_start) {
+    GFICF_HIP_CHECK(hipMemcpyAsync(w.W, d_start, sizeof(double) * (size_t)N * (size_t)b, hipMemcpyDeviceToDevice, st));
+    project(0, -1);
+    bw = b < mc ? b : mc;
+    nc = bw;
+    orth(0, bw);
+    GFICF_HIP_CHECK(hipGetLastError());
+    return GFICF_OK;
+  }
+
+  // one cycle: the basis grown to mc columns (capped by m: to its last full block), then the remainder of the last block and its
+  // Gram matrix.  From here to the restart nc is what the cycle ended with (me in spectral_ritz.h).
+  int grow() {
     for (;;) {
       mul(w.Xs, w.W);
       project(nc, c0);
-      if (nc == mc || (capped && mc - nc < b)) break;           // capped by m: no narrower block, no column of a remainder is discarded
+      if (nc == mc || (capped && mc - nc < b)) break;             // capped by m: no narrower block, no column of a remainder is discarded
       const int bwn = b < mc - nc ? b : mc - nc;
       orth(nc, bwn);
       c0 = nc; bw = bwn; nc += bwn;
     }
-    const int me = nc;                                          // the columns this cycle ended with
-    hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.W, b, b, (const double*)nullptr, (const double*)w.W, b, N, w.parts);
-    hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, b * b, w.G, (double*)nullptr, 0, 0, b, (double*)nullptr, 0);
+    gram(w.W);
     GFICF_HIP_CHECK(hipGetLastError());
+    return GFICF_OK;
+  }
+
+  // H, the Gram matrix, the column flags and the status word on the host: the cycle's one synchronisation
+  int read_cycle() {
     uint32_t hst = 0;
-    GFICF_HIP_CHECK(hipMemcpyAsync(hH.data(), w.H, sizeof(double) * (size_t)ldh * (size_t)me, hipMemcpyDeviceToHost, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(hH.data(), w.H, sizeof(double) * (size_t)ldh * (size_t)nc, hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipMemcpyAsync(hG.data(), w.G, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToHost, st));
-    GFICF_HIP_CHECK(hipMemcpyAsync(hflags.data(), w.flags, sizeof(int32_t) * (size_t)me, hipMemcpyDeviceToHost, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(hflags.data(), w.flags, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipMemcpyAsync(&hst, w.cc.status, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GFICF_HIP_CHECK(hipStreamSynchronize(st));
     if (hst & SP_ST_VALUE) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "a value of the graph that is not positive and finite");
-    // ---- Rayleigh-Ritz on the live columns
-    std::vector<int> live;
-    for (int j = 0; j < me; ++j)
-      if (j < keep || hflags[(size_t)j]) live.push_back(j);
-    const int n = (int)live.size();
+    return GFICF_OK;
+  }
+
+  // Rayleigh-Ritz on the live columns; *can_restart: restarts are left and there is more in the cycle than a restart would keep
+  int ritz(bool* can_restart) {
+    const int n = sp_ritz(nc, keep, bw, b, ldh, rs.kept.data(), hH.data(), hflags.data(), hG.data(), tol, rz);
     if (n < b) GFICF_FAIL(GFICF_ERR_BAD_VALUE, "the start block spans %d directions outside the trivial eigenvector, ndim = %d asked for", n, b);
-    A.assign((size_t)n * n, 0.0);
-    for (int x = 0; x < n; ++x)
-      for (int y = x; y < n; ++y) {
-        const int i = live[(size_t)x], j = live[(size_t)y];
-        const double h = j < keep ? (i == j ? kept[(size_t)i] : 0.0) : hH[(size_t)i + (size_t)ldh * (size_t)j];
-        A[(size_t)x * n + y] = A[(size_t)y * n + x] = h;
-      }
-    sp_jacobi(A, n, ev, Z);
-    Zfull.assign((size_t)me * n, 0.0);
-    for (int x = 0; x < n; ++x)
-      for (int l = 0; l < n; ++l) Zfull[(size_t)live[(size_t)x] * n + l] = Z[(size_t)x * n + l];
-    bool pass = true;
+    *can_restart = restarts < max_restarts && sp_keep_count(b, n) < nc;
+    return GFICF_OK;
+  }
+
+  // X = V Z[:, :b], signed; the residuals recomputed from one more multiplication, converged decided on them.  Synchronises.
+  int finish(double* d_X) {
+    sp_final_rotation(rz, nc, b, zb);
+    GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, zb.data(), sizeof(double) * zb.size(), hipMemcpyHostToDevice, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(w.theta, rz.theta.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * b)), dim3(256), 0, st, (const double*)V, ldv, nc, (const double*)w.Z, b, d_X, b, N);
+    hipLaunchKernelGGL(k_sp_amax_part, red, dim3(64), 0, st, (const double*)d_X, b, N, w.pv, w.pi);
+    hipLaunchKernelGGL(k_sp_sign_fin, one, dim3(64), 0, st, (const double*)d_X, b, (const double*)w.pv, (const int64_t*)w.pi, w.sign);
+    hipLaunchKernelGGL(k_sp_flip_scale, dim3(sp_grid(N * b)), dim3(256), 0, st, d_X, b, N, (const double*)w.sign, (const double*)w.dis, w.Xfs);
+    mul(w.Xfs, w.Wf);
+    with_block_width(b, [&](auto B) {
+      hipLaunchKernelGGL(k_sp_resid<decltype(B)::value>, rows, dim3(256), 0, st, w.Wf, (const double*)d_X, (const double*)w.theta, N);
+    });
+    gram(w.Wf);
+    GFICF_HIP_CHECK(hipGetLastError());
+    GFICF_HIP_CHECK(hipMemcpyAsync(hres.data(), w.G, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToHost, st));
+    GFICF_HIP_CHECK(hipStreamSynchronize(st));
+    converged = 1;
     for (int l = 0; l < b; ++l) {
-      double s = 0.0;
-      for (int x = 0; x < bw; ++x)
-        for (int y = 0; y < bw; ++y) s += Zfull[(size_t)(me - bw + x) * n + l] * hG[(size_t)x * b + y] * Zfull[(size_t)(me - bw + y) * n + l];
-      theta[(size_t)l] = ev[(size_t)l];
-      pass = pass && std::sqrt(s > 0.0 ? s : 0.0) <= tol * std::max(std::fabs(ev[(size_t)l]), eps23);
+      resid[(size_t)l] = std::sqrt(hres[(size_t)l * b + l] > 0.0 ? hres[(size_t)l * b + l] : 0.0);
+      if (!sp_within_tol(resid[(size_t)l], rz.theta[(size_t)l], tol)) converged = 0;
     }
-    const int kp = std::min(b + 2, n);
-    const bool can_restart = restarts < max_restarts && kp < me;
-    if (pass || !can_restart) {
-      // ---- X = V Z[:, :b], signed; the residuals recomputed from one more multiplication
-      up.assign((size_t)me * b, 0.0);
-      for (int j = 0; j < me; ++j)
-        for (int l = 0; l < b; ++l) up[(size_t)j * b + l] = Zfull[(size_t)j * n + l];
-      GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, st));
-      GFICF_HIP_CHECK(hipMemcpyAsync(w.theta, theta.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * b)), dim3(256), 0, st, (const double*)V, ldv, me, (const double*)w.Z, b, d_X, b, N);
-      hipLaunchKernelGGL(k_sp_amax_part, red, dim3(64), 0, st, (const double*)d_X, b, N, w.pv, w.pi);
-      hipLaunchKernelGGL(k_sp_sign_fin, one, dim3(64), 0, st, (const double*)d_X, b, (const double*)w.pv, (const int64_t*)w.pi, w.sign);
-      hipLaunchKernelGGL(k_sp_flip_scale, dim3(sp_grid(N * b)), dim3(256), 0, st, d_X, b, N, (const double*)w.sign, (const double*)w.dis, w.Xfs);
-      mul(w.Xfs, w.Wf);
-      SP_DISPATCH(b, k_sp_resid, rows, w.Wf, (const double*)d_X, (const double*)w.theta, N);
-      hipLaunchKernelGGL(k_sp_proj_part, red, dim3(256), 0, st, (const double*)w.Wf, b, b, (const double*)nullptr, (const double*)w.Wf, b, N, w.parts);
-      hipLaunchKernelGGL(k_sp_proj_fin, one, dim3(256), 0, st, (const double*)w.parts, b * b, w.G, (double*)nullptr, 0, 0, b, (double*)nullptr, 0);
-      GFICF_HIP_CHECK(hipGetLastError());
-      GFICF_HIP_CHECK(hipMemcpyAsync(hres.data(), w.G, sizeof(double) * (size_t)b * b, hipMemcpyDeviceToHost, st));
-      GFICF_HIP_CHECK(hipStreamSynchronize(st));
-      bool ok = true;
-      for (int l = 0; l < b; ++l) {
-        resid[(size_t)l] = std::sqrt(hres[(size_t)l * b + l] > 0.0 ? hres[(size_t)l * b + l] : 0.0);
-        ok = ok && resid[(size_t)l] <= tol * std::max(std::fabs(theta[(size_t)l]), eps23);
-      }
-      converged = ok ? 1 : 0;
-      if (ok || !can_restart) break;
-    }
-    // ---- thick restart: the leading kp Ritz vectors, then the residuals of the leading b as the next block
+    return GFICF_OK;
+  }
+
+  // thick restart: V <- V Z over the kept Ritz vectors, the residuals of the leading b (W_last Z_last) as the next block
+  int restart() {
     ++restarts;
-    std::vector<int> sel((size_t)kp);
-    for (int l = 0; l < kp; ++l) sel[(size_t)l] = l;
-    if (keep > 0 && n > kp && mc - kp < 2 * b) {
-      // one block per restarted cycle: the extra kept vectors are the Ritz vectors that carry most of the last leading b (rows < b of Z)
-      std::vector<double> carried((size_t)n, -1.0);
-      for (int l = b; l < n; ++l) {
-        double s = 0.0;
-        for (int i = 0; i < b; ++i) s += Zfull[(size_t)i * n + l] * Zfull[(size_t)i * n + l];
-        carried[(size_t)l] = s;
-      }
-      for (int x = b; x < kp; ++x) {
-        int at = -1;
-        for (int l = b; l < n; ++l)
-          if (carried[(size_t)l] >= 0.0 && (at < 0 || carried[(size_t)l] > carried[(size_t)at])) at = l;   // strict: the lowest index on ties
-        sel[(size_t)x] = at;
-        carried[(size_t)at] = -1.0;
-      }
-      std::sort(sel.begin() + b, sel.end());
-    }
-    up.assign((size_t)me * kp, 0.0);
-    for (int j = 0; j < me; ++j)
-      for (int l = 0; l < kp; ++l) up[(size_t)j * kp + l] = Zfull[(size_t)j * n + sel[(size_t)l]];
-    GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, st));
-    zl.assign((size_t)b * b, 0.0);
-    for (int x = 0; x < bw; ++x)
-      for (int l = 0; l < b; ++l) zl[(size_t)x * b + l] = Zfull[(size_t)(me - bw + x) * n + l];
-    GFICF_HIP_CHECK(hipMemcpyAsync(w.Zl, zl.data(), sizeof(double) * zl.size(), hipMemcpyHostToDevice, st));   // (up, zl: untouched until the next synchronisation)
-    hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * kp)), dim3(256), 0, st, (const double*)V, ldv, me, (const double*)w.Z, kp, Vo, ldv, N);
+    sp_restart_choice(rz, nc, keep, bw, b, mc, rs);
+    GFICF_HIP_CHECK(hipMemcpyAsync(w.Z, rs.up.data(), sizeof(double) * rs.up.size(), hipMemcpyHostToDevice, st));
+    GFICF_HIP_CHECK(hipMemcpyAsync(w.Zl, rs.zl.data(), sizeof(double) * rs.zl.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sp_rotate, dim3(sp_grid(N * rs.kp)), dim3(256), 0, st, (const double*)V, ldv, nc, (const double*)w.Z, rs.kp, Vo, ldv, N);
     std::swap(V, Vo);
-    SP_DISPATCH(b, k_sp_apply, rows, w.W, (const double*)w.Zl, N, (double*)nullptr, ldv, 0, 0, w.Xs, (const double*)w.dis);
-    keep = kp;
-    kept.assign((size_t)kp, 0.0);
-    for (int l = 0; l < kp; ++l) kept[(size_t)l] = ev[(size_t)sel[(size_t)l]];
+    with_block_width(b, [&](auto B) {
+      hipLaunchKernelGGL(k_sp_apply<decltype(B)::value>, rows, dim3(256), 0, st, w.W, (const double*)w.Zl, N, (double*)nullptr, ldv, 0, 0, w.Xs,
+                         (const double*)w.dis);
+    });
+    keep = rs.kp;
     project(keep, -1);
     bw = b < mc - keep ? b : mc - keep;
     orth(keep, bw);
     c0 = keep; nc = keep + bw;
     GFICF_HIP_CHECK(hipGetLastError());
+    return GFICF_OK;
   }
-  GFICF_HIP_CHECK(hipMemcpyAsync(d_theta, theta.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, st));
-  GFICF_HIP_CHECK(hipMemcpyAsync(d_resid, resid.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, st));
-  GFICF_HIP_CHECK(hipStreamSynchronize(st));
-  h_info[1] = restarts;
-  h_info[2] = mults;
-  h_info[3] = converged;
+};
+
+// the solve: theta, the residuals and the vectors on the device, h_info[1 .. 3] on the host.  Synchronises once per cycle, in every finish and at the end.
+int sp_solve(gficf_ctx* ctx, const SpWs& w, int64_t N, const int64_t* d_rowptr, const int32_t* d_col, const float* d_val, int b, const double* d_start,
+             double tol, int m, int max_restarts, double* d_theta, double* d_resid, double* d_X, int64_t* h_info) {
+  SpRun r(ctx, w, N, d_rowptr, d_col, d_val, b, tol, m, max_restarts);
+  GFICF_RC(r.prepare());
+  GFICF_RC(r.start(d_start));
+  for (;;) {
+    bool can_restart = false;
+    GFICF_RC(r.grow());
+    GFICF_RC(r.read_cycle());
+    GFICF_RC(r.ritz(&can_restart));
+    if (r.rz.pass || !can_restart) {
+      GFICF_RC(r.finish(d_X));
+      if (r.converged || !can_restart) break;
+    }
+    GFICF_RC(r.restart());
+  }
+  GFICF_HIP_CHECK(hipMemcpyAsync(d_theta, r.rz.theta.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, r.st));
+  GFICF_HIP_CHECK(hipMemcpyAsync(d_resid, r.resid.data(), sizeof(double) * (size_t)b, hipMemcpyHostToDevice, r.st));
+  GFICF_HIP_CHECK(hipStreamSynchronize(r.st));
+  h_info[1] = r.restarts;
+  h_info[2] = r.mults;
+  h_info[3] = r.converged;
   return GFICF_OK;
 }
 
@@ -756,9 +752,7 @@ int gficf_graph_components_device(gficf_ctx* ctx, int64_t N, const int64_t* d_ro
   if (capacity < 0) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "negative capacity");
   if (!d_rowptr || !d_labels || !d_info || !ws || (capacity > 0 && !d_col)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   CcWs w;
-  const size_t need = cc_carve(nullptr, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_CAPACITY, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  cc_carve((char*)ws, w);
+  GFICF_RC(sp_take(ws, ws_bytes, [&](char* base) { return cc_carve(base, w); }));
   int64_t comps = 0, rounds = 0;
   return cc_run(ctx, w, N, d_rowptr, d_col, capacity, d_labels, d_info, &comps, &rounds);
 }
@@ -773,21 +767,14 @@ int gficf_spectral_device(gficf_ctx* ctx, int64_t N, const int64_t* d_rowptr, co
                           const double* d_start, double tol, int m, int max_restarts, void* ws, size_t ws_bytes, double* d_theta, double* d_resid,
                           double* d_vectors, int64_t* d_info) {
   GFICF_CTX_ENTER(ctx);
-  int rc = sp_check(N, capacity, ndim, tol, m, max_restarts);
-  if (rc) return rc;
+  GFICF_RC(sp_check(N, capacity, ndim, tol, m, max_restarts));
   if (!d_rowptr || !d_start || !ws || !d_theta || !d_resid || !d_vectors || !d_info || (capacity > 0 && (!d_col || !d_val)))
     GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL device pointer");
   SpWs w;
-  const size_t need = sp_carve(nullptr, N, capacity, ndim, m, w);
-  if (ws_bytes < need) GFICF_FAIL(GFICF_ERR_CAPACITY, "workspace too small: %zu < %zu bytes", ws_bytes, need);
-  sp_carve((char*)ws, N, capacity, ndim, m, w);
+  GFICF_RC(sp_take(ws, ws_bytes, [&](char* base) { return sp_carve(base, N, capacity, ndim, m, w); }));
   int64_t info[4] = {0, 0, 0, 0}, rounds = 0;
-  rc = cc_run(ctx, w.cc, N, d_rowptr, d_col, capacity, w.labels, w.ccinfo, &info[0], &rounds);
-  if (rc) return rc;
-  if (info[0] == 1) {
-    rc = sp_solve(ctx, w, N, d_rowptr, d_col, d_val, ndim, d_start, tol, m, max_restarts, d_theta, d_resid, d_vectors, info);
-    if (rc) return rc;
-  }
+  GFICF_RC(cc_run(ctx, w.cc, N, d_rowptr, d_col, capacity, w.labels, w.ccinfo, &info[0], &rounds));
+  if (info[0] == 1) GFICF_RC(sp_solve(ctx, w, N, d_rowptr, d_col, d_val, ndim, d_start, tol, m, max_restarts, d_theta, d_resid, d_vectors, info));
   GFICF_HIP_CHECK(hipMemcpyAsync(d_info, info, sizeof(info), hipMemcpyHostToDevice, ctx->stream));
   GFICF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return GFICF_OK;
@@ -800,10 +787,8 @@ int gficf_spectral_host(gficf_ctx* ctx, int64_t N, const int64_t* rowptr, const 
   if (N < 1) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "N = %lld: no vertices", (long long)N);
   std::vector<int64_t> ptr;
   int64_t nnz = 0;
-  int rc = gficf_host_colptr(rowptr, 1, N, "rowptr", ptr, &nnz);
-  if (rc) return rc;
-  rc = sp_check(N, nnz, ndim, tol, m, max_restarts);
-  if (rc) return rc;
+  GFICF_RC(gficf_host_colptr(rowptr, 1, N, "rowptr", ptr, &nnz));
+  GFICF_RC(sp_check(N, nnz, ndim, tol, m, max_restarts));
   if (nnz > 0 && (!col || !val)) GFICF_FAIL(GFICF_ERR_INVALID_ARG, "NULL pointer");
   const size_t ws_b = gficf_spectral_workspace_bytes(N, nnz, ndim, m), nb = (size_t)N * (size_t)ndim, e = (size_t)(nnz > 0 ? nnz : 1);
   gficf_host_io io{ctx, "gficf_spectral_host"};
@@ -820,7 +805,7 @@ int gficf_spectral_host(gficf_ctx* ctx, int64_t N, const int64_t* rowptr, const 
   io.up(d_val, val, sizeof(float) * (size_t)nnz);
   io.up(d_start, start, sizeof(double) * nb);
   if (!io.ok()) return io.drain(GFICF_OK);
-  rc = gficf_spectral_device(ctx, N, d_rowptr, d_col, d_val, nnz, ndim, d_start, tol, m, max_restarts, d_ws, ws_b, d_theta, d_resid, d_X, d_info);
+  const int rc = gficf_spectral_device(ctx, N, d_rowptr, d_col, d_val, nnz, ndim, d_start, tol, m, max_restarts, d_ws, ws_b, d_theta, d_resid, d_X, d_info);
   if (rc) return io.drain(rc);
   io.down(info, d_info, sizeof(int64_t) * 4);
   if (labels) {                                                 // the labels of the entry's own components pass: the head of its workspace
@@ -828,8 +813,7 @@ int gficf_spectral_host(gficf_ctx* ctx, int64_t N, const int64_t* rowptr, const 
     sp_carve(d_ws, N, nnz, ndim, m, w);
     io.down(labels, w.labels, sizeof(int32_t) * (size_t)N);
   }
-  rc = io.drain(GFICF_OK);
-  if (rc) return rc;
+  GFICF_RC(io.drain(GFICF_OK));
   if (info[0] == 1) {
     io.down(theta, d_theta, sizeof(double) * (size_t)ndim);
     io.down(resid, d_resid, sizeof(double) * (size_t)ndim);
