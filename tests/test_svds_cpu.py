@@ -1,5 +1,5 @@
 """CPU: the numpy port of the exact truncated SVD (tests/helpers/svds_np.py) against LAPACK on the inputs of
-tests/test_svds_gpu.py; the exported surface of libgficf_svds.so; argument errors of the Python mirror."""
+tests/test_svds_gpu.py and on the case matrix of tests/helpers/svds_cases.py (every block width); the exported surface of libgficf_svds.so; argument errors of the Python mirror."""
 import os
 import re
 import shutil
@@ -10,6 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests.helpers import rsvd_np as rp
+from tests.helpers import svds_cases as sc
 from tests.helpers import svds_np as sn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,6 +56,41 @@ def test_port_matches_lapack_to_rounding(name):
     assert (g[i, np.arange(k)] > 0).all() and (np.diff(r["d"]) <= 1e-12 * r["d"][0]).all()
     if centre:
         assert np.allclose(r["centre"], M.toarray().mean(axis=1), rtol=1e-13, atol=0)
+
+
+@pytest.mark.parametrize("case", sc.ALL, ids=sc.case_id)
+def test_port_matches_lapack_at_every_width_and_basis_size(case):
+    """The rule of test_port_matches_lapack_to_rounding on the case matrix of tests/helpers/svds_cases.py: the port is the
+    yardstick of tests/test_svds_widths_gpu.py at block widths other than 8, so it is held to LAPACK there first."""
+    M, k = sc.matrix(case.matrix), case.k
+    w, r = sc.lapack(case.matrix, k, case.centre), sc.port(case)
+    dev = float(np.abs(r["d"][:len(w["d"])] - w["d"]).max() / w["d"][0])
+    print(sc.case_id(case), "d", dev, "cycles", r["cycles"], "products", r["products"], "converged", r["converged"], "exhausted", r["exhausted"])
+    assert dev < 64 * rp.EPS, (sc.case_id(case), dev)
+    assert r["converged"] == k or r["exhausted"]
+    nz = r["d"] > 0
+    g = r["genes"][:, nz]
+    assert np.abs(g.T @ g - np.eye(g.shape[1])).max() < 1e-12
+    i = np.argmax(np.abs(r["genes"]), axis=0)
+    assert (r["genes"][i, np.arange(k)][nz] > 0).all() and (np.diff(r["d"]) <= 1e-12 * r["d"][0]).all()
+    if case.centre:
+        assert np.allclose(r["centre"], M.toarray().mean(axis=1), rtol=1e-13, atol=0)
+    if case.group == "NARROW":
+        assert r["exhausted"] and r["cycles"] == 1 and (r["d"][sc.RANK:] == 0).all() and (r["d"][:min(k, sc.RANK)] > 0).all()
+        assert (r["genes"][:, sc.RANK:] == 0).all() and (r["cells"][:, sc.RANK:] == 0).all()
+    if case.group == "TINY":
+        assert r["exhausted"] and r["cycles"] == 1 and case.m == min(M.shape)
+
+
+def test_case_matrix_reaches_every_width_pitch_and_kept_count():
+    """The lists are what the issue of the widths set: every b of the contract at the tightest basis and at the widest, more
+    than 64 kept vectors, five chunks of rows, and only arguments the library accepts."""
+    assert sorted({c.b for c in sc.WIDTHS if c.matrix == "planted" and not c.centre}) == list(range(1, 33))
+    assert all(sn.check_args(min(sc.matrix(c.matrix).shape), c.k, c.b, c.m) for c in sc.ALL)
+    assert len({sc.case_id(c) for c in sc.ALL}) == len(sc.ALL)
+    assert all(min(c.k + c.b, c.m - c.b) > 64 for c in sc.MANY)                    # vectors kept at a restart from a full basis
+    assert min(sc.matrix("tall").shape) == 1100 and -(-1100 // 256) == 5 and 220 % 16 and 220 % 8
+    assert all(c.k == c.m == min(sc.matrix(c.matrix).shape) for c in sc.TINY)
 
 
 def test_port_flat_spectrum_where_the_sketch_is_percent_level_off():

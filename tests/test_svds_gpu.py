@@ -15,19 +15,15 @@ import scipy.sparse as sp
 
 import gficf_amd
 from gficf_amd import GficfError
-from gficf_amd.api import HipOps
 from tests.helpers import rsvd_np as rp
 from tests.helpers import svds_np as sn
+from tests.helpers.svds_cases import _device_form, _figures, _groups, _start, check_direct_residual, check_properties
 
 pytestmark = pytest.mark.gpu
 
 EPS = rp.EPS
 TOL = 1e-10
 SEED = 5
-
-
-def _start(n, b, seed=SEED + 1):
-    return np.random.default_rng(seed).standard_normal((n, b))
 
 
 def _sparse(nrows, ncols, density, seed, empty_every=7, zero_every=11):
@@ -85,51 +81,6 @@ def _case(name):
     return _cache[name]
 
 
-def _groups(d, gap):
-    """Runs of consecutive components whose values are closer than gap."""
-    out, cur = [], [0]
-    for i in range(1, len(d)):
-        if d[i - 1] - d[i] < gap:
-            cur.append(i)
-        else:
-            out.append(cur)
-            cur = [i]
-    out.append(cur)
-    return out
-
-
-def _figures(want, r):
-    """d relative to d[0]; cells / d[0] and genes, sign-aligned, a group of (nearly) coinciding values by its projector."""
-    d0 = want["d"][0]
-    kk = int((want["d"] > 1e-9 * d0).sum())                  # (the zero components of a rank below k: asserted apart)
-    fd = float(np.abs(r["d"][:len(want["d"])] - want["d"]).max() / d0)
-    fc = fg = 0.0
-    for g in _groups(want["d"][:kk], 1e-6 * d0):
-        wg, wc = want["genes"][:, g], want["cells"][:, g]
-        rg, rc = r["genes"][:, g], r["cells"][:, g]
-        if len(g) == 1:
-            fg = max(fg, float(np.abs(wg - rp.align(wg, rg)).max()))
-            fc = max(fc, float(np.abs(wc - rp.align(wc, rc)).max() / d0))
-        else:
-            dg = want["d"][g]
-            fg = max(fg, rp.projector_diff(wg, rg))
-            fc = max(fc, rp.projector_diff(wc / dg, rc / r["d"][g]) * float(dg[0] / d0))
-    return {"d": fd, "cells": fc, "genes": fg}
-
-
-def _At(M, centre):
-    A = sp.csc_matrix(M).T.toarray()
-    return A - A.mean(axis=0) if centre else A
-
-
-def _properties(M, centre, r):
-    """genes'genes = I over the non-zero components, cells = At genes relative to d[0], on the host in f64."""
-    nz = r["d"] > 0
-    g, d0 = r["genes"][:, nz], r["d"][0]
-    return {"orth": float(np.abs(g.T @ g - np.eye(g.shape[1])).max()),
-            "cells": float(np.abs(r["cells"] - _At(M, centre) @ r["genes"]).max() / d0)}
-
-
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_matches_lapack_within_the_ports_own_deviation(name):
     M, k, m, centre, start, want, port, got = _case(name)
@@ -149,27 +100,13 @@ def test_device_matches_lapack_within_the_ports_own_deviation(name):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_properties_orthonormal_genes_cells_sign_rule_order(name):
     M, k, m, centre, start, want, port, got = _case(name)
-    pp, pg = _properties(M, centre, port), _properties(M, centre, got)
-    print(name, "port", pp, "device", pg)
-    for q in pp:
-        assert pg[q] <= rp.tolerance(pp[q]), (name, q, pg[q], pp[q])
-    nz = got["d"] > 0
-    i = np.argmax(np.abs(got["genes"]), axis=0)
-    assert (got["genes"][i, np.arange(k)][nz] > 0).all()
-    assert (got["d"][:-1] >= got["d"][1:] * (1 - 1e-12)).all()
-    assert (got["genes"][:, ~nz] == 0).all() and (got["cells"][:, ~nz] == 0).all()
-    with np.errstate(divide="ignore", invalid="ignore"):
-        assert np.array_equal(got["u"], np.where(got["d"] > 0, got["cells"] / got["d"], 0.0))
+    check_properties(name, M, centre, k, port, got)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_direct_residual_on_the_host(name):
     M, k, m, centre, start, want, port, got = _case(name)
-    tau = rp.tau(max(M.shape))
-    rg, rq = sn.direct_residual(M, got, centre), sn.direct_residual(M, port, centre)
-    bound = np.maximum(TOL * got["d"] ** 2, tau * got["d"][0] ** 2) + rq
-    print(name, "device", rg.max() / got["d"][0] ** 2, "port", rq.max() / got["d"][0] ** 2, "worst ratio", (rg / bound).max())
-    assert (rg <= bound).all(), (name, rg, bound)
+    check_direct_residual(name, M, centre, port, got)
 
 
 def test_flat_spectrum_converges_where_the_sketch_is_percent_level_off():
@@ -203,30 +140,6 @@ def test_rank_below_k_gives_exact_zeros():
     assert np.abs(got["d"][:3] - d).max() / d[0] <= rp.tolerance(devp)
     assert (got["d"][3:] == 0).all() and (got["genes"][:, 3:] == 0).all() and (got["cells"][:, 3:] == 0).all() and got["exhausted"]
     assert np.abs(got["genes"][:, :3] - V).max() <= rp.tolerance(np.abs(port["genes"][:, :3] - V).max())
-
-
-def _device_form(M, k, b, m, centre, start, max_cycles=1000, ws_cut=0, colptr=None, x=None):
-    import torch
-
-    G, N = M.shape
-    ops = HipOps(0)
-    dev = torch.device("cuda", 0)
-    cp, ri, xv = (torch.from_numpy(a).to(dev) for a in ((M.indptr if colptr is None else colptr).astype(np.int64), M.indices.astype(np.int32),
-                                                        M.data if x is None else x))
-    sd = torch.from_numpy(np.ascontiguousarray(start.T)).to(dev)
-    d = torch.zeros(k, dtype=torch.float64, device=dev)
-    cells = torch.zeros((k, N), dtype=torch.float64, device=dev)
-    genes = torch.zeros((k, G), dtype=torch.float64, device=dev)
-    resid = torch.zeros(k, dtype=torch.float64, device=dev)
-    info = torch.zeros(4, dtype=torch.int64, device=dev)
-    mean = torch.zeros(G, dtype=torch.float64, device=dev)
-    need = ops.svds_workspace_bytes(G, N, M.nnz, k, b, m)
-    assert need > 0
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    ops.svds(G, N, cp, ri, xv, centre, sd, k, b, m, TOL, max_cycles, ws[: need - ws_cut], d, cells, genes, resid, info, mean)
-    ops.svds_sync(ws)
-    return {"d": d.cpu().numpy(), "cells": cells.cpu().numpy().T, "genes": genes.cpu().numpy().T, "residuals": resid.cpu().numpy(),
-            "info": info.cpu().numpy(), "centre": mean.cpu().numpy()}
 
 
 @pytest.mark.parametrize("name", ["restart_m40", "transposed", "centred"])
