@@ -2560,7 +2560,8 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     ``data["embedded"]`` becomes a pandas DataFrame with the columns ``X`` and ``Y`` (what ``clustcells(from_embedded=True)``
     searches), ``data["reduction"]`` the name, and with ``ret_model_pred`` ``data["uwot"]`` the dict of :func:`umap`.  Not provided,
     each raising ``NotImplementedError``: ``reduction="tsne"``, ``init="spectral"``, and a ``data`` without ``data["pca"]`` (the
-    reference then embeds the densified ``t(gficf)``).  ``nt`` is accepted for signature compatibility (no CPU threads)."""
+    reference then embeds ``t(gficf)`` itself: :func:`runReductionSparse` does, and the message names it).  ``nt`` is accepted for
+    signature compatibility (no CPU threads)."""
     import pandas as pd
 
     if reduction == "tsne":
@@ -2573,7 +2574,7 @@ def runReduction(data: dict, reduction: str = "tumap", nt: int = 2, seed: int = 
     o = dict(_REDUCTION_KW, **kw)
     if data.get("pca") is None:
         raise NotImplementedError("runReduction without data['pca'] (the reference embeds the densified t(gficf)) is not provided: "
-                                  "run runPCA or runLSA first")
+                                  "run runPCA or runLSA first, or call runReductionSparse, which searches the sparse cells")
     if o["metric"] not in _lib.KNN_METRICS:
         raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
     cells = np.asarray(data["pca"]["cells"], dtype=np.float64)
@@ -2800,8 +2801,8 @@ def runTsne(data: dict, seed: int = 18051982, verbose: bool = True, ctx: Context
     stop_lying_iter=None, mom_switch_iter=None, momentum=0.5, final_momentum=0.8, eta=200, exaggeration_factor=12, ret_P=False,
     ret_nn=False``).  ``data["embedded"]`` becomes a pandas DataFrame with the columns ``X`` and ``Y``, ``data["reduction"]``
     ``"tsne"`` and ``data["uwot"]`` None, as the reference leaves them; ``data["tsne"]`` keeps the rest of what :func:`Rtsne`
-    returned.  A ``data`` without ``data["pca"]`` raises ``NotImplementedError`` (the reference then embeds the densified
-    ``t(gficf)``)."""
+    returned.  A ``data`` without ``data["pca"]`` raises ``NotImplementedError`` (the reference then embeds ``t(gficf)`` itself:
+    ``runReductionSparse(reduction="tsne")`` does, and the message names it)."""
     import pandas as pd
 
     unknown = sorted(set(kw) - set(_TSNE_KW))
@@ -2809,7 +2810,7 @@ def runTsne(data: dict, seed: int = 18051982, verbose: bool = True, ctx: Context
         raise TypeError(f"runTsne: unknown argument(s) {unknown}")
     if data.get("pca") is None:
         raise NotImplementedError("runTsne without data['pca'] (the reference embeds the densified t(gficf)) is not provided: "
-                                  "run runPCA or runLSA first")
+                                  "run runPCA or runLSA first, or call runReductionSparse(reduction='tsne'), which searches the sparse cells")
     cells = np.asarray(data["pca"]["cells"], dtype=np.float64)
     tsmessage(f"Running tsne on {cells.shape[0]} cells, {cells.shape[1]} components", verbose=verbose)
     r = Rtsne(cells, dims=2, pca=False, seed=seed, ctx=ctx, **dict(_TSNE_KW, **kw))
@@ -2817,6 +2818,129 @@ def runTsne(data: dict, seed: int = 18051982, verbose: bool = True, ctx: Context
     data["reduction"] = "tsne"
     data["uwot"] = None
     data["tsne"] = r
+    return data
+
+
+# ------------------------------------------------------------------ embedding without PCA (libgficf_sparse_knn.so)
+SPARSE_REDUCTIONS = ("tumap", "umap", "tsne")
+
+
+def _sparse_centred_top(M) -> float:
+    """The largest magnitude of ``t(M)`` after its columns (the genes) are centred, without densifying it: Rtsne's
+    ``normalize_input`` divides by it, and centring itself moves no euclidean distance."""
+    import scipy.sparse as sp
+
+    M = sp.csc_matrix(M)
+    G, N = M.shape
+    mean = np.asarray(M.sum(axis=1)).ravel() / N
+    top = float(np.abs(M.data - mean[M.indices]).max()) if M.nnz else 0.0
+    absent = np.bincount(M.indices, minlength=G) < N               # genes some cell does not store: that cell holds -mean
+    return max(top, float(np.abs(mean[absent]).max()) if absent.any() else 0.0)
+
+
+def _reduction_sparse_umap(M, reduction, o, seed, ret_model_pred, ctx) -> dict:
+    N = M.shape[1]
+    k = int(o["n_neighbors"])
+    n_epochs = (500 if N <= 10000 else 200) if o["n_epochs"] is None else int(o["n_epochs"])
+    if reduction == "tumap":
+        a = b = 1.0
+    elif o["a"] is not None and o["b"] is not None:
+        a, b = float(o["a"]), float(o["b"])
+    else:
+        a, b = find_ab_params(o["spread"], o["min_dist"])
+    init = o["init"]
+    if isinstance(init, str) and init not in SPECTRAL_INITS + ("pca", "random"):
+        raise ValueError(f"init must be an N x 2 array or one of {SPECTRAL_INITS + ('pca', 'random')}")
+    nn = find_nn_sparse(M, k, True, o["metric"], ctx=ctx)
+    P = fuzzy_simplicial_set(nn["idx"], nn["dist"], o["set_op_mix_ratio"], o["local_connectivity"])[0]
+
+    def pca_start():
+        return umap_init("pca", rsvd(M, k=2, centre=True, ctx=ctx)["cells"], N, seed)
+
+    if isinstance(init, str) and init in SPECTRAL_INITS:
+        rng = np.random.default_rng(seed)
+        r = _spectral_solve(P, 2, start=rng.standard_normal((N, 2)))
+        if r["n_components"] > 1:
+            warnings.warn(f"found more than one component ({r['n_components']}) in the graph: falling back to init='pca'")
+            Y0 = pca_start()
+        else:
+            if not r["converged"]:
+                warnings.warn(f"spectral initialisation not converged after {r['restarts']} restarts (residuals {r['residuals']})")
+            Y0 = _spectral_coordinates(r["vectors"], rng, init == "spectral")
+    elif isinstance(init, str) and init == "pca":
+        Y0 = pca_start()
+    else:
+        Y0 = umap_init(init, None, N, seed)
+    Y = umap_layout(P, Y0, n_epochs, a, b, o["learning_rate"], o["negative_sample_rate"], o["repulsion_strength"],
+                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return {"embedding": Y.astype(np.float64), "graph": P if ret_model_pred else None, "nn": nn if ret_model_pred else None, "a": float(a),
+            "b": float(b), "n_neighbors": k, "metric": o["metric"], "n_epochs": n_epochs, "seed": int(seed), "space": "gficf"}
+
+
+def _reduction_sparse_tsne(M, o, seed, ctx) -> dict:
+    N = M.shape[1]
+    k = _tsne_k(o["perplexity"], N)
+    given = o["Y_init"] is not None
+    Y0 = _tsne_state(o["Y_init"], N, "Y_init", 0.0) if given else np.random.default_rng(seed).standard_normal((N, 2)) * 1e-4
+    stop_lying_iter = (0 if given else 250) if o["stop_lying_iter"] is None else int(o["stop_lying_iter"])
+    mom_switch_iter = (0 if given else 250) if o["mom_switch_iter"] is None else int(o["mom_switch_iter"])
+    nn = find_nn_sparse(M, k, True, "euclidean", ctx=ctx)
+    if o["normalize"]:
+        top = _sparse_centred_top(M)
+        if top > 0:
+            nn["dist"] = nn["dist"] / top
+    P = tsne_affinities(nn["idx"], nn["dist"], o["perplexity"])[0]
+    Y, kl = tsne_layout(P, Y0, int(o["max_iter"]), stop_lying_iter=stop_lying_iter, mom_switch_iter=mom_switch_iter, momentum=o["momentum"],
+                        final_momentum=o["final_momentum"], eta=o["eta"], exaggeration_factor=o["exaggeration_factor"], ret_kl=True)
+    return {"Y": Y.astype(np.float64), "N": N, "perplexity": float(o["perplexity"]), "costs": kl, "theta": float(o["theta"]),
+            "max_iter": int(o["max_iter"]), "eta": float(o["eta"]), "stop_lying_iter": stop_lying_iter, "mom_switch_iter": mom_switch_iter,
+            "momentum": float(o["momentum"]), "final_momentum": float(o["final_momentum"]), "exaggeration_factor": float(o["exaggeration_factor"]),
+            "P": P if o["ret_P"] else None, "nn": nn if o["ret_nn"] else None, "space": "gficf"}
+
+
+def runReductionSparse(data: dict, reduction: str = "tumap", seed: int = 18051982, ret_model_pred: bool = True, verbose: bool = True,
+                       ctx: Context | None = None, **kw) -> dict:
+    """The ``data$pca``-less branch of the reference's ``runReduction`` (R/dimensinalityReduction.R:179-187: ``tumap``, ``umap``
+    or ``Rtsne`` of ``t(data$gficf)``) on the device, composed from the stages the package has; the cells are never densified:
+    the neighbour search is :func:`find_nn_sparse` over the columns of ``data["gficf"]``.
+
+    ``"tumap"`` / ``"umap"``: :func:`find_nn_sparse` -> :func:`fuzzy_simplicial_set` -> start -> :func:`umap_layout`, with
+    :func:`runReduction`'s keywords.  ``init`` is ``"spectral"`` (the default HERE, as uwot's: :func:`spectral_init`'s solve of the
+    graph; a graph of more than one component warns, naming the count, and starts from ``"pca"``), ``"normlaplacian"``,
+    ``"pca"`` (``rsvd(data["gficf"], k=2, centre=True)["cells"]`` through :func:`umap_init`'s scaling), ``"random"`` or an N x 2
+    array.  ``"tsne"``: ``find_nn_sparse(euclidean, floor(3 perplexity) + 1)`` -> :func:`tsne_affinities` ->
+    :func:`tsne_layout`, with :func:`runTsne`'s keywords and start; ``normalize`` divides the distances by the largest magnitude
+    of the gene-centred matrix, which is what Rtsne's ``normalize_input`` does to them.
+
+    ``data["embedded"]``, ``data["reduction"]`` and ``data["uwot"]`` (``data["tsne"]`` for t-SNE) are set as :func:`runReduction`
+    and :func:`runTsne` set them; the model carries ``"space": "gficf"`` and its ``nn`` table.  :func:`embedNewCells` refuses such
+    a model (the reference's needs ``data$pca`` too)."""
+    import pandas as pd
+
+    if reduction not in SPARSE_REDUCTIONS:
+        raise ValueError(f"reduction must be one of {SPARSE_REDUCTIONS}")
+    defaults = _TSNE_KW if reduction == "tsne" else dict(_REDUCTION_KW, init="spectral")
+    unknown = sorted(set(kw) - set(defaults))
+    if unknown:
+        raise TypeError(f"runReductionSparse: unknown argument(s) {unknown}")
+    o = dict(defaults, **kw)
+    if data.get("gficf") is None:
+        raise ValueError("runReductionSparse needs data['gficf']: run gficf first")
+    if reduction != "tsne" and o["metric"] not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    M = data["gficf"]
+    tsmessage(f"Running {reduction} on {M.shape[1]} cells, {M.shape[0]} genes (sparse)", verbose=verbose)
+    if reduction == "tsne":
+        r = _reduction_sparse_tsne(M, o, seed, ctx)
+        data["embedded"] = pd.DataFrame(r.pop("Y"), columns=["X", "Y"])
+        data["uwot"] = None
+        data["tsne"] = r
+    else:
+        r = _reduction_sparse_umap(M, reduction, o, seed, ret_model_pred, ctx)
+        data["embedded"] = pd.DataFrame(r["embedding"], columns=["X", "Y"])
+        if ret_model_pred:
+            data["uwot"] = r
+    data["reduction"] = reduction
     return data
 
 
@@ -2968,6 +3092,9 @@ def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: boo
                                   "run runTsne on the old and the new cells together")
     if data.get("uwot") is None:
         raise ValueError("embedNewCells needs the trained model: run runReduction(ret_model_pred=True) first")
+    if data["uwot"].get("space") == "gficf":
+        raise NotImplementedError("embedNewCells on a model of runReductionSparse (trained on the sparse cells, not on data['pca']; the "
+                                  "reference's embedNewCells needs data$pca too) is not provided: run runPCA and runReduction")
     unknown = sorted(set(kw) - set(_TRANSFORM_KW))
     if unknown:
         raise TypeError(f"embedNewCells: unknown argument(s) {unknown}")
@@ -3040,8 +3167,14 @@ def find_nn(X, k: int, include_self: bool = True, metric: str = "manhattan", ctx
     ctx = ctx or default_context()
     check(_lib.load().gficf_knn_host(ctx.handle, _np_ptr(X), N, d, max(N, 1), kk, _lib.KNN_METRICS[metric],
                                      _np_ptr(idx), _np_ptr(dist)))
-    idx, dist = idx.T, dist.T
+    return _nn_table(idx.T, dist.T, include_self)
+
+
+def _nn_table(idx, dist, include_self: bool) -> dict:
+    """The return of :func:`find_nn` and :func:`find_nn_sparse` from the N x kk table searched; without ``include_self`` kk was
+    k + 1 and the row's own id leaves every list."""
     if not include_self:
+        N, kk = idx.shape
         own = np.arange(1, N + 1, dtype=np.int32)[:, None]
         is_self = idx == own
         drop = np.where(is_self.any(axis=1), is_self.argmax(axis=1), kk - 1)   # self absent (duplicates): drop the last
@@ -3049,6 +3182,89 @@ def find_nn(X, k: int, include_self: bool = True, metric: str = "manhattan", ctx
         keep[np.arange(N), drop] = False
         idx, dist = idx[keep].reshape(N, kk - 1), dist[keep].reshape(N, kk - 1)
     return {"idx": np.ascontiguousarray(idx), "dist": np.ascontiguousarray(dist)}
+
+
+# ------------------------------------------------------------------ kNN over sparse cells (libgficf_sparse_knn.so)
+def find_nn_sparse_shape(G: int, N: int, k: int) -> dict:
+    """The decomposition of the sparse search for ``G`` genes, ``N`` cells and ``k`` neighbours (``gficf_sparse_knn_shape``, a host
+    query): ``{"tile_queries", "slices", "max_genes"}``: the query cells a workgroup holds densely in LDS (8, 4, 2 or 1, the
+    fewer the more genes), the ranges the candidates are cut into when N / tile_queries workgroups would not fill the chip, and
+    the largest ``G`` the search takes.  Arguments the search refuses (``G > max_genes`` among them) raise its error."""
+    from . import _sparse_knn_lib
+
+    tq, s, mg = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    check(_sparse_knn_lib.load().gficf_sparse_knn_shape(int(G), int(N), int(k), ctypes.byref(tq), ctypes.byref(s), ctypes.byref(mg)))
+    return {"tile_queries": tq.value, "slices": s.value, "max_genes": mg.value}
+
+
+def _sparse_cells(M, metric):
+    """The genes x cells CSC parts of ``M`` for the sparse search, after the checks the library would only report deferred: row
+    ids inside [0, G) and strictly ascending within a column, values finite as float32."""
+    if metric not in _lib.KNN_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
+    if np.ndim(M) != 2:
+        raise ValueError("M must be a 2-d genes x cells matrix")
+    M, colptr, rowidx, x = _csc_parts(M)
+    G, N = M.shape
+    if G < 1 or N < 1:
+        raise ValueError(f"M is {G} x {N}: the matrix needs a gene and a cell")
+    if len(rowidx):
+        if rowidx.min() < 0 or rowidx.max() >= G:
+            raise ValueError(f"row ids must lie in [0, {G})")
+        step = np.diff(rowidx) > 0
+        step[colptr[1:-1][(colptr[1:-1] > 0) & (colptr[1:-1] < len(rowidx))] - 1] = True    # the seam between two columns
+        if not step.all():
+            raise ValueError("row ids must be strictly ascending within a column (sort_indices, sum_duplicates)")
+        with np.errstate(over="ignore"):
+            if not np.isfinite(x.astype(np.float32)).all():
+                raise ValueError("the values must be finite as float32")
+    return G, N, colptr, rowidx, x
+
+
+def find_nn_sparse(M, k: int, include_self: bool = True, metric: str = "euclidean", ctx: Context | None = None) -> dict:
+    """:func:`find_nn` for sparse cells: the exact neighbour search over the columns of the genes x cells matrix ``M`` (scipy
+    sparse, taken as CSC; what :func:`gficf` returns as ``data["gficf"]``) without densifying it (``gficf_sparse_knn_host``,
+    include/gficf_sparse_knn.h: values rounded to float32 once, pair sums in float64 over the shared genes, one rounding of the
+    distance to float32).  Cosine on GF-ICF is the text-retrieval reading of this normalisation.
+
+    Returns ``{"idx": N x k int32 (1-based), "dist": N x k float64}``, the k smallest (distance, id) pairs per cell, ties broken
+    by the smaller id; with ``include_self`` column 0 is the cell itself (or an identical cell with a smaller id); without it the
+    cell's own id is removed from every list (k+1 are searched).  ``idx`` is what :func:`jaccard_edges`,
+    :func:`fuzzy_simplicial_set` and :func:`tsne_affinities` take.  More genes than ``find_nn_sparse_shape(...)["max_genes"]``
+    raise ``GFICF_ERR_UNSUPPORTED``."""
+    from . import _sparse_knn_lib
+
+    G, N, colptr, rowidx, x = _sparse_cells(M, metric)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    kk = k if include_self else k + 1
+    idx = np.zeros((kk, N), dtype=np.int32)          # C-order (kk, N) == column-major N x kk
+    dist = np.zeros((kk, N), dtype=np.float64)
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_sparse_knn_lib.load().gficf_sparse_knn_host(ctx.handle, G, N, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), kk,
+                                                       _lib.KNN_METRICS[metric], _np_ptr(idx), _np_ptr(dist)))
+    return _nn_table(idx.T, dist.T, include_self)
+
+
+def find_nn_sparse_range(M, k: int, q_begin: int, q_end: int, metric: str = "euclidean", device: int = 0) -> dict:
+    """The rows ``[q_begin, q_end)`` of :func:`find_nn_sparse`'s table (``include_self=True``) through the device entry
+    (``gficf_sparse_knn_device``): running ``[0, a)`` and ``[a, N)`` gives the bits of ``[0, N)``."""
+    G, N, colptr, rowidx, x = _sparse_cells(M, metric)
+    k, q_begin, q_end = int(k), int(q_begin), int(q_end)
+    if k < 1 or not 0 <= q_begin <= q_end <= N:
+        raise ValueError(f"k must be at least 1 and [q_begin, q_end) lie in [0, {N}]")
+    n_q = q_end - q_begin
+    ops = _umap_hip(device)
+    tc, dev = ops.torch, f"cuda:{device}"
+    d_cp, d_ri, d_x = (tc.from_numpy(v).to(dev) for v in (colptr.astype(np.int64), rowidx, x))
+    ws = tc.empty(max(ops.sparse_knn_workspace_bytes(G, N, len(rowidx), k, n_q), 1), dtype=tc.uint8, device=dev)
+    idx = tc.zeros((k, max(n_q, 1)), dtype=tc.int32, device=dev)
+    dist = tc.zeros((k, max(n_q, 1)), dtype=tc.float64, device=dev)
+    ops.sparse_knn(G, N, d_cp, d_ri, d_x, k, metric, q_begin, q_end, ws, idx, dist)
+    ops.sparse_knn_sync(ws)
+    return {"idx": np.ascontiguousarray(idx.cpu().numpy().T[:n_q]), "dist": np.ascontiguousarray(dist.cpu().numpy().T[:n_q])}
 
 
 def clustcells_graph(X, k: int = 15, dist_method: str = "manhattan", verbose: bool = False, ctx: Context | None = None) -> dict:
@@ -3806,6 +4022,31 @@ class HipOps:
         from . import _svds_lib
 
         check(_svds_lib.load().gficf_svds_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def sparse_knn_workspace_bytes(G: int, N: int, nnz: int, k: int, n_queries: int) -> int:
+        """Device scratch of ``sparse_knn`` (libgficf_sparse_knn.so); 0 on arguments it would refuse."""
+        from . import _sparse_knn_lib
+
+        return int(_sparse_knn_lib.load().gficf_sparse_knn_workspace_bytes(int(G), int(N), int(nnz), int(k), int(n_queries)))
+
+    def sparse_knn(self, G, n_cells, colptr, rowidx, x, k, metric, q_begin, q_end, ws, idx_cm, dist_cm=None):
+        """Exact kNN of the cells [q_begin, q_end) among all ``n_cells`` sparse cells on device-resident tensors (colptr int64,
+        rowidx int32, x float64: the genes x cells CSC matrix; ws uint8 of ``sparse_knn_workspace_bytes``); idx_cm: (k, n_q) int32
+        == column-major n_q x k, 1-based; dist_cm alike, float64, optional.  Enqueues only: call ``sparse_knn_sync(ws)`` to wait
+        and to collect the deferred input errors."""
+        from . import _sparse_knn_lib
+
+        n_q = int(q_end) - int(q_begin)
+        check(_sparse_knn_lib.load().gficf_sparse_knn_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x),
+                                                             int(rowidx.numel()), int(k), _lib.KNN_METRICS[metric], int(q_begin), int(q_end),
+                                                             _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(idx_cm), _tptr(dist_cm),
+                                                             max(n_q, 1)))
+
+    def sparse_knn_sync(self, ws):
+        from . import _sparse_knn_lib
+
+        check(_sparse_knn_lib.load().gficf_sparse_knn_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def csc_tmm_workspace_bytes(nrows: int, ncols: int, nnz: int, l: int) -> int:
