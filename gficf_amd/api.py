@@ -1544,7 +1544,7 @@ def run_modularity_clustering(SNN, modularity: int = 1, resolution: float = 0.8,
     if modularity == 2 and resolution > 1.0:
         raise ValueError("error: resolution<1 for alternative modularity")
     if algorithm not in (1, 2):
-        raise ValueError("algorithm must be 1 (Louvain) or 2 (Louvain with multilevel refinement)")
+        raise ValueError("algorithm must be 1 (Louvain) or 2 (Louvain with multilevel refinement); algorithm 3 (smart local moving) is slm()")
     if n_start < 1 or n_iter < 1:
         raise ValueError("n_start and n_iter must be at least 1")
     A = sp.csc_matrix(SNN)
@@ -1651,6 +1651,56 @@ def leiden_refine(A, labels, resolution: float = 1.0, ctx: Context | None = None
     check(_leiden_lib.load().gficf_leiden_refine_host(ctx.handle, N, _np_ptr(indptr), _np_ptr(indices), _np_ptr(x), len(indices), float(resolution),
                                                       _np_ptr(lab), _np_ptr(out), ctypes.byref(nr)))
     return out[:N]
+
+
+def slm(A, resolution: float = 0.8, n_start: int = 10, n_iter: int = 10, seed: int = 0, init=None, ctx: Context | None = None):
+    """The smart local moving algorithm (Waltman, van Eck 2013) on a symmetric weighted adjacency matrix: ``algorithm = 3`` of the
+    reference's ``RunModularityClustering`` (src/ModularityOptimizer.cpp:651-690), as a function of its own.
+
+    RELAXED CONTRACT (include/gficf_slm.h): the algorithm and its objective are SLM's — the level loop of :func:`leiden` with a
+    full local moving inside every community, from singletons, where Leiden merges singletons once — the visiting order and the
+    random bits are not the reference's.  ``n_start`` runs with seeds ``seed + s``, the one of largest modularity returned (ties:
+    the first); ``n_iter`` iterations each, fewer when an iteration returns its own start.  The result is a function of the
+    arguments, bit for bit.  ``init``: a start partition (labels in [0, N)).
+
+    Returns ``ClusterLabels`` (int32, 0-based, clusters numbered by decreasing size) with ``.modularity``, ``.n_clusters``,
+    ``.start`` (the start the result came from) and ``.iterations`` (how many that start ran).
+    """
+    from . import _slm_lib
+
+    if n_start < 1 or n_iter < 1:
+        raise ValueError("n_start and n_iter must be at least 1")
+    N, indptr, indices, x = _leiden_matrix(A, resolution)
+    start = None if init is None else _leiden_labels(init, N, "init")
+    labels = np.zeros(max(N, 1), dtype=np.int32)
+    info = _slm_lib.Info()
+    ctx = ctx or default_context()
+    check(_slm_lib.load().gficf_slm_host(ctx.handle, N, _np_ptr(indptr), _np_ptr(indices), _np_ptr(x), len(indices), float(resolution),
+                                         int(n_start), int(n_iter), int(seed) & 0xFFFFFFFF, None if start is None else _np_ptr(start),
+                                         _np_ptr(labels), ctypes.byref(info)))
+    out = labels[:N].view(ClusterLabels)
+    out.modularity, out.n_clusters, out.start, out.iterations = info.modularity, info.n_clusters, info.start, info.iterations
+    return out
+
+
+def slm_submove(A, labels, resolution: float = 1.0, seed: int = 0, level: int = 0, ctx: Context | None = None):
+    """The sub-moving stage of :func:`slm` alone on the finest graph: local moving from singletons inside every community of
+    ``labels`` (include/gficf_slm.h, step 3).  Returns int32[N], the smallest member id of every vertex's sub-community, with
+    ``.n_clusters`` (their number) and ``.passes``."""
+    from . import _slm_lib
+
+    if level < 0:
+        raise ValueError("level must not be negative")
+    N, indptr, indices, x = _leiden_matrix(A, resolution)
+    lab = _leiden_labels(labels, N, "labels")
+    out = np.zeros(max(N, 1), dtype=np.int32)
+    info = _slm_lib.SubmoveInfo()
+    ctx = ctx or default_context()
+    check(_slm_lib.load().gficf_slm_submove_host(ctx.handle, N, _np_ptr(indptr), _np_ptr(indices), _np_ptr(x), len(indices), float(resolution),
+                                                 _np_ptr(lab), int(seed) & 0xFFFFFFFF, int(level), _np_ptr(out), ctypes.byref(info)))
+    out = out[:N].view(ClusterLabels)
+    out.n_clusters, out.passes = info.n_sub, info.passes
+    return out
 
 
 def transpose_gficf(gficf_mat, ctx: Context | None = None):
@@ -3298,7 +3348,7 @@ def phenograph(X, k: int = 15, dist_method: str = "manhattan", resolution: float
     return out
 
 
-COMMUNITY_ALGOS = ("louvian", "louvian 2", "louvian 3", "leiden")
+COMMUNITY_ALGOS = ("louvian", "louvian 2", "louvian 3", "leiden", "slm")
 
 
 def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method: str = "manhattan", nt: int = 2,
@@ -3313,6 +3363,8 @@ def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method
     ``"gficf"`` (genes x cells CSC).  ``community_algo``: "louvian 2" / "louvian 3" (resolution, n_iter as given) or
     "louvian" (the reference calls igraph::cluster_louvain there: plain modularity, i.e. resolution 1) or "leiden"
     (:100-107: :func:`leiden` with ``resolution``, two iterations and ``seed``; relaxed contract of include/gficf_leiden.h);
+    or "slm" (an extension: the reference's ``match.arg`` has no such choice and its "louvian 3" is algorithm 2 of the optimiser;
+    :func:`slm`, algorithm 3, with ``resolution``, ``n_start``, ``n_iter`` and ``seed``, filling what "louvian 2" fills);
     the igraph algorithms "walktrap" and "fastgreedy" are third-party and not provided.  ``nt`` is accepted for
     signature compatibility (no CPU threads); ``seed`` and ``n_start`` act as in ``run_modularity_clustering``.  Returns ``data`` updated with ``community``
     (1-based like the reference), ``cluster`` (the labels as strings, ``data$embedded$cluster``), ``cluster.gene.rnk``
@@ -3335,6 +3387,10 @@ def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method
         edges = clustcells_graph(X, k, dist_method, verbose, ctx)
         A = jaccard_adjacency(edges, N, ctx)
         community = leiden(A, resolution, 2, seed, None, ctx)
+    elif community_algo == "slm":                             # staged as well
+        edges = clustcells_graph(X, k, dist_method, verbose, ctx)
+        A = jaccard_adjacency(edges, N, ctx)
+        community = slm(A, resolution, n_start, n_iter, seed, None, ctx)
     elif store_graph:
         edges = clustcells_graph(X, k, dist_method, verbose, ctx)
         A = jaccard_adjacency(edges, N, ctx)
@@ -4309,6 +4365,33 @@ class HipOps:
                                                             float(resolution), _tptr(labels_in), _tptr(refined), ctypes.byref(nr), _tptr(ws),
                                                             int(ws.numel() * ws.element_size())))
         return nr.value
+
+    def slm_workspace_bytes(self, N: int, nnz: int) -> int:
+        """Device scratch of ``slm`` and ``slm_submove``."""
+        from . import _slm_lib
+
+        return int(_slm_lib.load().gficf_slm_workspace_bytes(int(N), int(nnz)))
+
+    def slm(self, N, indptr, indices, x, resolution, n_start, n_iter, labels, ws, seed: int = 0, init=None):
+        """Smart local moving on a device-resident symmetric adjacency matrix (indptr int64, indices int32, x float64); init: int32[N]
+        or None.  Returns (n_clusters, modularity, start, iterations); labels: int32[N]."""
+        from . import _slm_lib
+
+        info = _slm_lib.Info()
+        check(_slm_lib.load().gficf_slm_device(self._bind(), int(N), _tptr(indptr), _tptr(indices), _tptr(x), int(indices.numel()), float(resolution),
+                                               int(n_start), int(n_iter), int(seed) & 0xFFFFFFFF, _tptr(init), _tptr(ws),
+                                               int(ws.numel() * ws.element_size()), _tptr(labels), ctypes.byref(info)))
+        return info.n_clusters, info.modularity, info.start, info.iterations
+
+    def slm_submove(self, N, indptr, indices, x, resolution, labels_in, sub, ws, seed: int = 0, level: int = 0):
+        """The sub-moving stage alone; sub: int32[N], the smallest member id of every vertex's sub-community.  Returns (their number, passes)."""
+        from . import _slm_lib
+
+        info = _slm_lib.SubmoveInfo()
+        check(_slm_lib.load().gficf_slm_submove_device(self._bind(), int(N), _tptr(indptr), _tptr(indices), _tptr(x), int(indices.numel()),
+                                                       float(resolution), _tptr(labels_in), int(seed) & 0xFFFFFFFF, int(level), _tptr(ws),
+                                                       int(ws.numel() * ws.element_size()), _tptr(sub), ctypes.byref(info)))
+        return info.n_sub, info.passes
 
     def csc_transpose_workspace_bytes(self, G: int, n_cells: int) -> int:
         return int(self.L.gficf_csc_transpose_workspace_bytes(int(G), int(n_cells)))

@@ -38,7 +38,7 @@
 //   * n_start "random starts": each start varies the seed of the class hash (the only arbitrary choice there is); the best
 //     modularity wins, as in the reference.  Start 0 with seed 0 is the plain run.
 //   * the alternative modularity function (2): unit node weights, the resolution as given — a context option.
-// Not reproduced: algorithm 3 (SLM).
+// Algorithm 3 is refused by these entries: it is slm.hip's, an add-on of its own (include/gficf_slm.h).
 //
 // Round 6 — the starts in ONE launch set, the iterations without host round trips:
 //   * the n_start starts are independent problems on one graph.  They run as ONE problem on the disjoint union of B copies
