@@ -4088,16 +4088,21 @@ class HipOps:
 
     def sparse_knn(self, G, n_cells, colptr, rowidx, x, k, metric, q_begin, q_end, ws, idx_cm, dist_cm=None):
         """Exact kNN of the cells [q_begin, q_end) among all ``n_cells`` sparse cells on device-resident tensors (colptr int64,
-        rowidx int32, x float64: the genes x cells CSC matrix; ws uint8 of ``sparse_knn_workspace_bytes``); idx_cm: (k, n_q) int32
-        == column-major n_q x k, 1-based; dist_cm alike, float64, optional.  Enqueues only: call ``sparse_knn_sync(ws)`` to wait
-        and to collect the deferred input errors."""
+        rowidx int32, x float64: the genes x cells CSC matrix; ws uint8 of ``sparse_knn_workspace_bytes``); idx_cm: (k, ld) int32,
+        contiguous, ld >= n_q == column-major n_q x k with leading dimension ld (the entries [n_q, ld) of a row are not written),
+        1-based; dist_cm alike, float64, optional.  Enqueues only: call ``sparse_knn_sync(ws)`` to wait and to collect the deferred
+        input errors."""
         from . import _sparse_knn_lib
 
         n_q = int(q_end) - int(q_begin)
+        if idx_cm.dim() != 2 or idx_cm.shape[0] != int(k) or idx_cm.shape[1] < max(n_q, 1) or not idx_cm.is_contiguous():
+            raise ValueError("idx_cm must be a contiguous (k, ld) tensor with ld >= the number of queries")
+        if dist_cm is not None and (dist_cm.shape != idx_cm.shape or not dist_cm.is_contiguous()):
+            raise ValueError("dist_cm must be contiguous and shaped like idx_cm")
         check(_sparse_knn_lib.load().gficf_sparse_knn_device(self._bind(), int(G), int(n_cells), _tptr(colptr), _tptr(rowidx), _tptr(x),
                                                              int(rowidx.numel()), int(k), _lib.KNN_METRICS[metric], int(q_begin), int(q_end),
                                                              _tptr(ws), int(ws.numel() * ws.element_size()), _tptr(idx_cm), _tptr(dist_cm),
-                                                             max(n_q, 1)))
+                                                             int(idx_cm.shape[1])))
 
     def sparse_knn_sync(self, ws):
         from . import _sparse_knn_lib
