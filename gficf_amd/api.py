@@ -2964,7 +2964,7 @@ def runReductionSparse(data: dict, reduction: str = "tumap", seed: int = 1805198
 
     ``data["embedded"]``, ``data["reduction"]`` and ``data["uwot"]`` (``data["tsne"]`` for t-SNE) are set as :func:`runReduction`
     and :func:`runTsne` set them; the model carries ``"space": "gficf"`` and its ``nn`` table.  :func:`embedNewCells` refuses such
-    a model (the reference's needs ``data$pca`` too)."""
+    a model (the reference's needs ``data$pca`` too): :func:`embedNewCellsSparse` takes it."""
     import pandas as pd
 
     if reduction not in SPARSE_REDUCTIONS:
@@ -3144,7 +3144,8 @@ def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: boo
         raise ValueError("embedNewCells needs the trained model: run runReduction(ret_model_pred=True) first")
     if data["uwot"].get("space") == "gficf":
         raise NotImplementedError("embedNewCells on a model of runReductionSparse (trained on the sparse cells, not on data['pca']; the "
-                                  "reference's embedNewCells needs data$pca too) is not provided: run runPCA and runReduction")
+                                  "reference's embedNewCells needs data$pca too) is not provided: use embedNewCellsSparse, or run runPCA and "
+                                  "runReduction")
     unknown = sorted(set(kw) - set(_TRANSFORM_KW))
     if unknown:
         raise TypeError(f"embedNewCells: unknown argument(s) {unknown}")
@@ -3168,13 +3169,15 @@ def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: boo
     return data
 
 
-CLASSIFY_METHODS = ("PCA", "embedded")
+CLASSIFY_METHODS = ("PCA", "embedded", "gficf")
 
 
 def classify_cells(data: dict, classes, k: int = 7, seed: int = 18051982, method: str = "PCA", ctx: Context | None = None):
     """``classify.cells(data, classes, k, seed, method)`` of the reference (R/cellClassifier.R:15-29): the new cells of
     :func:`embedNewCells` labelled by :func:`knn_classify` from the trained ones, whose labels ``classes`` are.  ``"PCA"`` searches
-    ``data["pca"]["cells"]`` against ``data["pca"]["pred"]``; ``"embedded"`` the NO rows of the plane against the YES rows.
+    ``data["pca"]["cells"]`` against ``data["pca"]["pred"]``; ``"embedded"`` the NO rows of the plane against the YES rows;
+    ``"gficf"`` the sparse columns of ``data["gficf"]`` against ``data["gficf.pred"]`` of :func:`embedNewCellsSparse`
+    (:func:`knn_classify_sparse`).
     Returns a DataFrame ``cell.id`` (the new cells' row labels in ``data["embedded"]``), ``pred``.  ``seed`` is accepted for
     the signature: nothing is random here."""
     import pandas as pd
@@ -3185,6 +3188,11 @@ def classify_cells(data: dict, classes, k: int = 7, seed: int = 18051982, method
     if emb is None or "predicted" not in getattr(emb, "columns", ()):
         raise ValueError("Please embed first new cells!")
     new = np.asarray(emb["predicted"].astype(str) == "YES")
+    if method == "gficf":
+        if data.get("gficf.pred") is None:
+            raise ValueError("method='gficf' needs data['gficf.pred']: embed the new cells with embedNewCellsSparse")
+        pred = knn_classify_sparse(data["gficf"], data["gficf.pred"], np.asarray(classes).astype(str), k, "euclidean", ctx)
+        return pd.DataFrame({"cell.id": list(emb.index[new]), "pred": pred})
     if method == "PCA":
         train, test = data["pca"]["cells"], data["pca"]["pred"]
     else:
@@ -3247,17 +3255,17 @@ def find_nn_sparse_shape(G: int, N: int, k: int) -> dict:
     return {"tile_queries": tq.value, "slices": s.value, "max_genes": mg.value}
 
 
-def _sparse_cells(M, metric):
+def _sparse_cells(M, metric, name: str = "M", min_cells: int = 1):
     """The genes x cells CSC parts of ``M`` for the sparse search, after the checks the library would only report deferred: row
     ids inside [0, G) and strictly ascending within a column, values finite as float32."""
     if metric not in _lib.KNN_METRICS:
         raise ValueError(f"metric must be one of {sorted(_lib.KNN_METRICS)}")
     if np.ndim(M) != 2:
-        raise ValueError("M must be a 2-d genes x cells matrix")
+        raise ValueError(f"{name} must be a 2-d genes x cells matrix")
     M, colptr, rowidx, x = _csc_parts(M)
     G, N = M.shape
-    if G < 1 or N < 1:
-        raise ValueError(f"M is {G} x {N}: the matrix needs a gene and a cell")
+    if G < 1 or N < min_cells:
+        raise ValueError(f"{name} is {G} x {N}: the matrix needs a gene and a cell")
     if len(rowidx):
         if rowidx.min() < 0 or rowidx.max() >= G:
             raise ValueError(f"row ids must lie in [0, {G})")
@@ -3315,6 +3323,195 @@ def find_nn_sparse_range(M, k: int, q_begin: int, q_end: int, metric: str = "euc
     ops.sparse_knn(G, N, d_cp, d_ri, d_x, k, metric, q_begin, q_end, ws, idx, dist)
     ops.sparse_knn_sync(ws)
     return {"idx": np.ascontiguousarray(idx.cpu().numpy().T[:n_q]), "dist": np.ascontiguousarray(dist.cpu().numpy().T[:n_q])}
+
+
+# ------------------------------------------------------------------ new sparse cells among trained ones (libgficf_sparse_query.so)
+def find_nn_sparse_query_shape(G: int, N: int, M: int, k: int) -> dict:
+    """The decomposition of the search of ``M`` sparse query cells among ``N`` training cells over ``G`` genes
+    (``gficf_sparse_query_shape``, a host query): ``{"tile_queries", "slices", "max_genes"}``, the rule of
+    :func:`find_nn_sparse_shape` for M queries against N candidates.  Arguments the search refuses raise its error."""
+    from . import _sparse_query_lib
+
+    tq, s, mg = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    check(_sparse_query_lib.load().gficf_sparse_query_shape(int(G), int(N), int(M), int(k), ctypes.byref(tq), ctypes.byref(s), ctypes.byref(mg)))
+    return {"tile_queries": tq.value, "slices": s.value, "max_genes": mg.value}
+
+
+def _sparse_pair(M_train, Q, metric):
+    """The CSC parts of the training cells and of the queries (which may have no columns), over the same genes."""
+    t = _sparse_cells(M_train, metric, "M_train")
+    q = _sparse_cells(Q, metric, "Q", min_cells=0)
+    if t[0] != q[0]:
+        raise ValueError(f"Q has {q[0]} rows (genes), M_train has {t[0]}")
+    return t, q
+
+
+def find_nn_sparse_query(M_train, Q, k: int, metric: str = "euclidean", ctx: Context | None = None) -> dict:
+    """:func:`find_nn_query` for sparse cells: the ``k`` nearest columns of ``M_train`` (genes x N, scipy sparse, taken as CSC:
+    ``data["gficf"]``) for every column of ``Q`` (genes x M, the same genes), exact, neither matrix densified
+    (``gficf_sparse_query_host``, include/gficf_sparse_query.h: the method of :func:`find_nn_sparse` word for word, without its
+    self rule).  A query equal to a training cell is at exactly 0 under euclidean and manhattan and within 2^-51 of 0 under
+    cosine and correlation.  Returns ``{"idx": M x k int32, 1-based ids of training cells, "dist": M x k float64}``; a ``Q``
+    without columns gives empty tables."""
+    from . import _sparse_query_lib
+
+    (G, N, tcp, tri, tx), (_, M, qcp, qri, qx) = _sparse_pair(M_train, Q, metric)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    idx = np.zeros((k, max(M, 1)), dtype=np.int32)          # C-order (k, M) == column-major M x k
+    dist = np.zeros((k, max(M, 1)), dtype=np.float64)
+    ctx = ctx or default_context()
+    check(_sparse_query_lib.load().gficf_sparse_query_host(
+        ctx.handle, G, N, _np_ptr(tcp), 1 if tcp.dtype == np.int64 else 0, _np_ptr(tri), _np_ptr(tx), M, _np_ptr(qcp),
+        1 if qcp.dtype == np.int64 else 0, _np_ptr(qri), _np_ptr(qx), k, _lib.KNN_METRICS[metric], _np_ptr(idx), _np_ptr(dist)))
+    return {"idx": np.ascontiguousarray(idx.T[:M]), "dist": np.ascontiguousarray(dist.T[:M])}
+
+
+def _sparse_query_enqueue(ops, t, q, k, metric, want_f32: bool):
+    """Both matrices uploaded and the search enqueued: (ws, idx (k, M) int32, dist32 (k, M) float32 or None) on the device."""
+    (G, N, tcp, tri, tx), (_, M, qcp, qri, qx) = t, q
+    tc, dev = ops.torch, f"cuda:{ops.device}"
+    d_t = [tc.from_numpy(v).to(dev) for v in (tcp.astype(np.int64), tri, tx)]
+    d_q = [tc.from_numpy(v).to(dev) for v in (qcp.astype(np.int64), qri, qx)]
+    ws = tc.empty(max(ops.sparse_query_workspace_bytes(G, N, len(tri), M, len(qri), k), 1), dtype=tc.uint8, device=dev)
+    idx = tc.zeros((k, M), dtype=tc.int32, device=dev)
+    dist32 = tc.zeros((k, M), dtype=tc.float32, device=dev) if want_f32 else None
+    ops.sparse_query(G, N, *d_t, M, *d_q, k, metric, ws, idx, None, dist32)
+    return ws, idx, dist32
+
+
+def umap_transform_sparse(Q, model: dict, M_train, n_epochs: int | None = None, learning_rate: float | None = None,
+                          negative_sample_rate: int = 5, repulsion_strength: float = 1.0, local_connectivity: float = 1.0,
+                          seed: int | None = None, init="weighted", query_offset: int = 0, epoch_begin: int = 0, epoch_end: int | None = None,
+                          ret_extra: bool = False, ctx: Context | None = None):
+    """:func:`umap_transform` for a model of :func:`runReductionSparse` (``model["space"] == "gficf"``): the place of the columns
+    of ``Q`` (genes x M sparse) in the plane of ``model``, trained on the columns of ``M_train`` (genes x N sparse,
+    ``data["gficf"]``).  The same keywords, defaults and ``ret_extra`` dict as :func:`umap_transform`, and its stages on the
+    device, chained through :class:`HipOps` without a host copy between them: ``sparse_query`` (float32 distances) ->
+    ``transform_weights`` -> ``transform_init`` (or the given ``init``) -> ``transform_layout``.  The result for column i
+    depends on that column, the model and ``query_offset + i`` only: a batch may be cut into pieces."""
+    if model.get("space") != "gficf":
+        raise ValueError("umap_transform_sparse needs a model of runReductionSparse (model['space'] == 'gficf'): use umap_transform")
+    metric, k = model["metric"], int(model["n_neighbors"])
+    t, q = _sparse_pair(M_train, Q, metric)
+    N, M = t[1], q[1]
+    Yt = np.ascontiguousarray(model["embedding"], dtype=np.float64)
+    if Yt.shape != (N, 2):
+        raise ValueError(f"model['embedding'] must be N x 2 = {N} x 2: M_train is not what the model was trained on")
+    if n_epochs is None:
+        n_epochs = max(1, int(round(model["n_epochs"] / 3)))
+    epoch_end = int(n_epochs) if epoch_end is None else int(epoch_end)
+    learning_rate = 0.25 if learning_rate is None else float(learning_rate)
+    seed = int(model["seed"]) if seed is None else int(seed)
+    Y0 = None
+    if not (isinstance(init, str) and init == "weighted"):
+        if isinstance(init, str):
+            raise ValueError("init must be 'weighted' or an M x 2 array")
+        Y0 = np.ascontiguousarray(init, dtype=np.float64)
+        if Y0.shape != (M, 2):
+            raise ValueError(f"init must be 'weighted' or an M x 2 = {M} x 2 array")
+        if not np.isfinite(Y0).all():
+            raise ValueError("init must be finite")
+    if M == 0:
+        emb = np.zeros((0, 2))
+        if not ret_extra:
+            return emb
+        return {"embedding": emb, "idx": np.zeros((0, k), np.int32), "dist": np.zeros((0, k), np.float32), "w": np.zeros((0, k), np.float32),
+                "sigma": np.zeros(0, np.float32), "rho": np.zeros(0, np.float32), "init": np.zeros((0, 2))}
+    ops = _umap_hip(ctx.device if ctx is not None else 0)
+    tc, dev = ops.torch, f"cuda:{ops.device}"
+    sws, idx, dist = _sparse_query_enqueue(ops, t, q, k, metric, True)
+    d_Yt = tc.from_numpy(Yt.astype(np.float32)).to(dev)
+    w = tc.zeros((k, M), dtype=tc.float32, device=dev)
+    sigma, rho = (tc.zeros(M, dtype=tc.float32, device=dev) for _ in range(2))
+    wws, iws, lws = (tc.empty(max(ops.transform_workspace_bytes(s, M, k=k), 1), dtype=tc.uint8, device=dev) for s in ("weights", "init", "layout"))
+    ops.transform_weights(idx, dist, N, M, k, wws, w, local_connectivity, sigma, rho)
+    stages = [wws, lws]
+    if Y0 is None:
+        Y = tc.zeros((M, 2), dtype=tc.float32, device=dev)
+        ops.transform_init(idx, w, d_Yt, N, M, k, iws, Y)
+        stages.insert(1, iws)
+    else:
+        Y = tc.from_numpy(Y0.astype(np.float32)).to(dev)
+    y0 = Y.clone() if ret_extra else None
+    ops.transform_layout(idx, w, d_Yt, N, M, k, float(model["a"]), float(model["b"]), float(repulsion_strength), learning_rate,
+                         int(negative_sample_rate), int(n_epochs), int(epoch_begin), epoch_end, seed, int(query_offset), Y, lws)
+    ops.sparse_query_sync(sws)                                # waits for the stream; every status word after it is a read
+    for ws in stages:
+        ops.transform_sync(ws)
+    emb = Y.cpu().numpy().astype(np.float64)
+    if not ret_extra:
+        return emb
+    host = lambda a: np.ascontiguousarray(a.cpu().numpy().T)
+    return {"embedding": emb, "idx": host(idx), "dist": host(dist), "w": host(w), "sigma": sigma.cpu().numpy(), "rho": rho.cpu().numpy(),
+            "init": y0.cpu().numpy().astype(np.float64)}
+
+
+def knn_classify_sparse(train, test, classes, k: int = 7, metric: str = "euclidean", ctx: Context | None = None) -> np.ndarray:
+    """:func:`knn_classify` for sparse cells: for every column of ``test`` (genes x M sparse) the class with the most votes among
+    its ``k`` nearest columns of ``train`` (genes x N sparse), ``sparse_query`` -> ``transform_vote`` on the device.  The label
+    handling and the tie rule are :func:`knn_classify`'s.  ``classes``: one label per column of ``train``."""
+    t, q = _sparse_pair(train, test, metric)
+    N, M, k = t[1], q[1], int(k)
+    classes = np.asarray(classes)
+    if classes.shape != (N,):
+        raise ValueError(f"classes must hold one label per column of train: {N}")
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    levels, codes = np.unique(classes, return_inverse=True)
+    if M == 0:
+        return levels[np.zeros(0, dtype=np.int64)]
+    ops = _umap_hip(ctx.device if ctx is not None else 0)
+    tc, dev = ops.torch, f"cuda:{ops.device}"
+    sws, idx, _ = _sparse_query_enqueue(ops, t, q, k, metric, False)
+    labels = tc.from_numpy(np.ascontiguousarray(codes, dtype=np.int32)).to(dev)
+    pred = tc.zeros(M, dtype=tc.int32, device=dev)
+    vws = tc.empty(max(ops.transform_workspace_bytes("vote", M, k=k), 1), dtype=tc.uint8, device=dev)
+    ops.transform_vote(idx, labels, N, M, k, max(len(levels), 1), vws, pred)
+    ops.sparse_query_sync(sws)
+    ops.transform_sync(vws)
+    return levels[pred.cpu().numpy()]
+
+
+def embedNewCellsSparse(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: bool = True, genes=None, ctx: Context | None = None,
+                        **kw) -> dict:
+    """:func:`embedNewCells` without the PCA step, for a model of :func:`runReductionSparse`: the new cells are GF-ICF
+    normalised with the trained ICF weights (:func:`gficf_with_weights`) and placed into the trained plane by their sparse
+    columns (:func:`umap_transform_sparse` against ``data["gficf"]``, which ``**kw`` goes to: the keywords of
+    :func:`embedNewCells`).  ``x`` and ``genes`` are :func:`embedNewCells`'s.  ``data["embedded"]`` gets the column
+    ``predicted`` as there; ``data["gficf.pred"]`` holds the new cells' GF-ICF columns (kept genes x new cells, CSC), which is
+    what ``classify_cells(method="gficf")`` searches.  ``nt`` and ``seed`` are accepted for the signature."""
+    import scipy.sparse as sp
+
+    if data.get("reduction") == "tsne":
+        raise NotImplementedError("embedNewCellsSparse after reduction='tsne' (the reference re-runs Rtsne) is not provided: "
+                                  "run runReductionSparse(reduction='tsne') on the old and the new cells together")
+    if data.get("uwot") is None:
+        raise ValueError("embedNewCellsSparse needs the trained model: run runReductionSparse(ret_model_pred=True) first")
+    if data["uwot"].get("space") != "gficf":
+        raise ValueError("embedNewCellsSparse needs a model of runReductionSparse (trained on the sparse cells); this one was trained "
+                         "on data['pca']: use embedNewCells")
+    unknown = sorted(set(kw) - set(_TRANSFORM_KW))
+    if unknown:
+        raise TypeError(f"embedNewCellsSparse: unknown argument(s) {unknown}")
+    if data.get("gficf") is None:
+        raise ValueError("embedNewCellsSparse needs data['gficf']: run gficf first")
+    rows = np.asarray(data["genes"] if genes is None else genes, dtype=np.int64)
+    if rows.shape != (len(data["w"]),):
+        raise ValueError("genes must name one row of x for every kept gene (len(data['w']))")
+    x = sp.csc_matrix(x)
+    if len(rows) and (rows.min() < 0 or rows.max() >= x.shape[0]):
+        raise ValueError(f"x has {x.shape[0]} rows: the kept genes name rows up to {int(rows.max())}")
+    tsmessage(f"Embedding {x.shape[1]} new cells (sparse)", verbose=verbose)
+    sub = x[rows, :]
+    g, kept = gficf_with_weights(sub, data["w"], ctx)
+    # the rows gficf_with_weights dropped as empty come back (as empty rows): one per row of data["gficf"]
+    g = sp.csc_matrix((g.data, kept[g.indices].astype(np.int32), g.indptr), shape=(len(rows), x.shape[1]))
+    xy = umap_transform_sparse(g, data["uwot"], data["gficf"], ctx=ctx, **kw)
+    data["embedded"] = _append_predicted(data["embedded"], xy)
+    data["gficf.pred"] = g
+    return data
 
 
 def clustcells_graph(X, k: int = 15, dist_method: str = "manhattan", verbose: bool = False, ctx: Context | None = None) -> dict:
@@ -4108,6 +4305,38 @@ class HipOps:
         from . import _sparse_knn_lib
 
         check(_sparse_knn_lib.load().gficf_sparse_knn_sync(self._bind(), _tptr(ws)))
+
+    @staticmethod
+    def sparse_query_workspace_bytes(G: int, N: int, nnz_train: int, M: int, nnz_query: int, k: int) -> int:
+        """Device scratch of ``sparse_query`` (libgficf_sparse_query.so); 0 on arguments it would refuse."""
+        from . import _sparse_query_lib
+
+        return int(_sparse_query_lib.load().gficf_sparse_query_workspace_bytes(int(G), int(N), int(nnz_train), int(M), int(nnz_query), int(k)))
+
+    def sparse_query(self, G, n_train, t_colptr, t_rowidx, t_x, n_query, q_colptr, q_rowidx, q_x, k, metric, ws, idx_cm, dist_cm=None,
+                     dist32_cm=None):
+        """Exact kNN of the ``n_query`` sparse cells of one genes x cells CSC matrix among the ``n_train`` of another, both
+        device-resident (colptr int64, rowidx int32, x float64; ws uint8 of ``sparse_query_workspace_bytes``); idx_cm: (k, ld)
+        int32, contiguous, ld >= n_query == column-major n_query x k with leading dimension ld (the entries [n_query, ld) of a row
+        are not written), 1-based training ids; dist_cm (float64) and dist32_cm (float32) alike, each optional.  Enqueues only:
+        call ``sparse_query_sync(ws)`` to wait and to collect the deferred input errors of both matrices."""
+        from . import _sparse_query_lib
+
+        n_query = int(n_query)
+        if idx_cm.dim() != 2 or idx_cm.shape[0] != int(k) or idx_cm.shape[1] < max(n_query, 1) or not idx_cm.is_contiguous():
+            raise ValueError("idx_cm must be a contiguous (k, ld) tensor with ld >= the number of queries")
+        for name, t, dt in (("dist_cm", dist_cm, self.torch.float64), ("dist32_cm", dist32_cm, self.torch.float32)):
+            if t is not None and (t.shape != idx_cm.shape or not t.is_contiguous() or t.dtype != dt):
+                raise ValueError(f"{name} must be contiguous, {dt} and shaped like idx_cm")
+        check(_sparse_query_lib.load().gficf_sparse_query_device(
+            self._bind(), int(G), int(n_train), _tptr(t_colptr), _tptr(t_rowidx), _tptr(t_x), int(t_rowidx.numel()), n_query, _tptr(q_colptr),
+            _tptr(q_rowidx), _tptr(q_x), int(q_rowidx.numel()), int(k), _lib.KNN_METRICS[metric], _tptr(ws), int(ws.numel() * ws.element_size()),
+            _tptr(idx_cm), _tptr(dist_cm), _tptr(dist32_cm), int(idx_cm.shape[1])))
+
+    def sparse_query_sync(self, ws):
+        from . import _sparse_query_lib
+
+        check(_sparse_query_lib.load().gficf_sparse_query_sync(self._bind(), _tptr(ws)))
 
     @staticmethod
     def csc_tmm_workspace_bytes(nrows: int, ncols: int, nnz: int, l: int) -> int:
