@@ -170,7 +170,7 @@ __device__ __forceinline__ void knn_reg_insert(u64 (&lst)[EPL], u64 key) {
 // Arguments of the tile kernel.  Queries and candidates are separate row-major arrays of dpad floats per row (dpad = d rounded
 // up to 4, zero padded): the square search passes Q = X + q_begin rows in its plain form and its two reordered copies in its
 // pruned form; the transform passes the new cells and the trained ones.  A value-initialised struct with the members up to
-// `part` filled in is the plain form without a gate.
+// `part` filled in is the plain form without a gate: knn_plain_args below.
 struct KnnTileArgs {
   const float* Q;          // n_q query rows
   int64_t n_q;
@@ -186,12 +186,21 @@ struct KnnTileArgs {
   uint32_t gate_want;
 };
 
+// The plain form's arguments: no gate, no permutation, no bounds.  Host only (no device code comes of it).
+inline KnnTileArgs knn_plain_args(const float* Q, int64_t n_q, const float* X, int64_t N, int d, int dpad, int k, int S, u64* part) {
+  KnnTileArgs a{};
+  a.Q = Q; a.n_q = n_q; a.X = X; a.N = N;
+  a.d = d; a.dpad = dpad; a.kk = k; a.S = S;
+  a.part = part;
+  return a;
+}
+
 // One workgroup = one tile of TQ = 16 * RQ queries x a sequence of candidate tiles.
 //   PRUNE == false: the candidate tiles of slice sp of S, in order (an empty slice writes its untouched lists: all ~0).
 //   PRUNE == true : S = 1; the candidate tiles in the order of their lower bound lb[qt][*], best first, and the
 //     sequence ends at the first tile whose bound exceeds the largest k-th best distance of the tile's queries —
 //     no point of that tile or of any later one can enter a list (the bound is a triangle-inequality bound
-//     with slack for f32 rounding, built by knn.hip's k_knn_lb).  The next tile is chosen by every wave for itself from
+//     with slack for f32 rounding, built by knn_prune.h's k_knn_lb).  The next tile is chosen by every wave for itself from
 //     the same LDS data (bounds, visited marks and the waves' k-th best maxima published one tile earlier,
 //     double-buffered), so the waves agree without an extra barrier.
 template <int METRIC, int KL, int RQ, bool PRUNE>

@@ -325,10 +325,7 @@ int tr_search(gficf_ctx* ctx, u64* part, const float* d_train, int64_t N, const 
               float* d_dist, int64_t ld_out) {
   if (M == 0) return GFICF_OK;
   metric = gficf_knn_search_metric(metric);
-  KnnTileArgs a{};                                                // the plain form: no gate, no permutation, no bounds
-  a.Q = d_query; a.n_q = M; a.X = d_train; a.N = N; a.d = d; a.dpad = gficf_knn_dpad(d); a.kk = k;
-  a.S = tr_split(ctx->num_cus, M, N);
-  a.part = part;
+  const KnnTileArgs a = knn_plain_args(d_query, M, d_train, N, d, gficf_knn_dpad(d), k, tr_split(ctx->num_cus, M, N), part);
   const int rc = knn_launch_m<false>(ctx, metric, a);
   if (rc) return rc;
   hipLaunchKernelGGL(k_tr_merge, dim3(tr_grid(M, 4)), dim3(256), 0, ctx->stream, (const u64*)part, M, a.S, k, metric, d_idx, d_dist, ld_out);

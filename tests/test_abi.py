@@ -91,6 +91,19 @@ def test_every_louvain_kernel_header_compiles_on_its_own():
         assert r.returncode == 0, h + ".h:\n" + r.stderr[-2000:]
 
 
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_every_knn_kernel_header_compiles_on_its_own():
+    """The headers of knn.hip include what they use: knn_tiles.h (the tile kernel it shares with transform.hip) and knn_prune.h
+    (the pruned search's preparation)."""
+    import subprocess
+
+    csrc = os.path.join(ROOT, "gficf_amd", "csrc")
+    for h in ("knn_tiles", "knn_prune"):
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", "-x", "hip",
+                            os.path.join(csrc, h + ".h")], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, h + ".h:\n" + r.stderr[-2000:]
+
+
 def test_status_enum_matches_header():
     src = open(os.path.join(ROOT, "include", "gficf_hip.h")).read()
     for code, name in _lib.STATUS_NAMES.items():
