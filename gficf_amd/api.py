@@ -3151,6 +3151,7 @@ def embedNewCells(data: dict, x, nt: int = 2, seed: int = 18051982, verbose: boo
         raise TypeError(f"embedNewCells: unknown argument(s) {unknown}")
     if data.get("pca") is None:
         raise ValueError("First run runPCA or runLSA to reduce dimensionality")
+    _refuse_after_harmony(data, "embedNewCells")
     rows = np.asarray(data["genes"] if genes is None else genes, dtype=np.int64)
     if rows.shape != (len(data["w"]),):
         raise ValueError("genes must name one row of x for every kept gene (len(data['w']))")
@@ -3194,6 +3195,7 @@ def classify_cells(data: dict, classes, k: int = 7, seed: int = 18051982, method
         pred = knn_classify_sparse(data["gficf"], data["gficf.pred"], np.asarray(classes).astype(str), k, "euclidean", ctx)
         return pd.DataFrame({"cell.id": list(emb.index[new]), "pred": pred})
     if method == "PCA":
+        _refuse_after_harmony(data, "classify_cells(method='PCA')")
         train, test = data["pca"]["cells"], data["pca"]["pred"]
     else:
         xy = np.asarray(emb[["X", "Y"]], dtype=np.float64)
@@ -3603,6 +3605,314 @@ def clustcells(data: dict, from_embedded: bool = False, k: int = 15, dist_method
         data["cluster.gene.rnk"], data["cluster.labels"] = cluster_signatures(data["gficf"], data["cluster"], ctx)
     tsmessage(f"Detected Clusters: {community.n_clusters}", verbose=verbose)       # reference R/clustCells.R:125
     return data
+
+
+# ------------------------------------------------------------------ Harmony: batch correction of the PCA cells
+_HARMONY_OPS: dict = {}
+
+
+def _harmony_ops(device: int = 0):
+    """The stage object the Harmony mirrors enqueue on (one per device, made at the first call)."""
+    if device not in _HARMONY_OPS:
+        _HARMONY_OPS[device] = HipOps(device)
+    return _HARMONY_OPS[device]
+
+
+def harmony_levels(batch, N: int):
+    """``batch`` (a vector, or a DataFrame or dict of vectors: V variables) as the library takes it: ``levels`` (V, N) int32 global
+    level ids, ``var_start`` int32 of V + 1, and per variable its name and its labels in order of first appearance."""
+    from . import _harmony_lib
+
+    if hasattr(batch, "columns") and hasattr(batch, "__getitem__"):
+        cols = [(str(c), np.asarray(batch[c])) for c in batch.columns]
+    elif isinstance(batch, dict):
+        cols = [(str(c), np.asarray(v)) for c, v in batch.items()]
+    else:
+        cols = [("batch", np.asarray(batch))]
+    if not 1 <= len(cols) <= _harmony_lib.MAX_V:
+        raise ValueError(f"batch must give 1 to {_harmony_lib.MAX_V} variables, not {len(cols)}")
+    levels, var_start, names, labels = [], [0], [], []
+    for name, col in cols:
+        if col.shape != (N,):
+            raise ValueError(f"batch variable {name!r} must hold one label per cell ({N}), not {col.shape}")
+        ids, lab = _first_appearance_ids(col, N)
+        levels.append(ids + var_start[-1])
+        var_start.append(var_start[-1] + len(lab))
+        names.append(name)
+        labels.append(lab)
+    if var_start[-1] > _harmony_lib.MAX_B:
+        raise ValueError(f"batch has {var_start[-1]} levels in all: at most {_harmony_lib.MAX_B}")
+    return np.ascontiguousarray(np.stack(levels), dtype=np.int32), np.asarray(var_start, dtype=np.int32), names, labels
+
+
+def harmony_draws(N: int, K: int, rounds: int, seed: int = 180582):
+    """The random inputs of a run, drawn in this order from ``np.random.default_rng(seed)``: K distinct cells (the start
+    centroids), then one permutation of the cells per clustering round: ``(cells, perm)``, ``perm`` (rounds, N) int32."""
+    rng = np.random.default_rng(seed)
+    cells = rng.choice(N, K, replace=False)
+    perm = np.empty((rounds, N), dtype=np.int32)
+    for r in range(rounds):
+        perm[r] = rng.permutation(N)
+    return cells, perm
+
+
+def _harmony_check_shapes(Z, levels, var_start, K=None):
+    from . import _harmony_lib
+
+    Z = np.ascontiguousarray(Z, dtype=np.float64)
+    if Z.ndim != 2 or Z.shape[0] < 1 or not 1 <= Z.shape[1] <= _harmony_lib.MAX_D:
+        raise ValueError(f"the cells must be an N x d matrix with 1 <= d <= {_harmony_lib.MAX_D}")
+    if not np.isfinite(Z).all():
+        raise ValueError("the cells hold a value that is not finite")
+    N = Z.shape[0]
+    if levels is not None:
+        levels = np.ascontiguousarray(levels, dtype=np.int32)
+        var_start = np.ascontiguousarray(var_start, dtype=np.int32)
+        if levels.ndim != 2 or levels.shape[1] != N or not 1 <= levels.shape[0] <= _harmony_lib.MAX_V:
+            raise ValueError(f"levels must be V x N with 1 <= V <= {_harmony_lib.MAX_V}")
+        V = levels.shape[0]
+        if var_start.shape != (V + 1,) or var_start[0] != 0 or (np.diff(var_start) < 1).any() or var_start[-1] > _harmony_lib.MAX_B:
+            raise ValueError(f"var_start must rise from 0 by at least 1 a variable to B <= {_harmony_lib.MAX_B}")
+        if ((levels < var_start[:-1, None]) | (levels >= var_start[1:, None])).any():
+            raise ValueError("a level id lies outside its variable's range")
+    if K is not None and not 1 <= K <= min(N, _harmony_lib.MAX_K):
+        raise ValueError(f"the number of clusters must be in [1, min(N, {_harmony_lib.MAX_K})], not {K}")
+    return Z, levels, var_start
+
+
+def _harmony_per_level(x, var_start, what, lo=0.0):
+    """A scalar, one value per variable or one per level, as one float64 per level."""
+    B, V = int(var_start[-1]), len(var_start) - 1
+    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    if x.shape == (1,):
+        x = np.full(B, x[0])
+    elif x.shape == (V,) and V != B:
+        x = np.repeat(x, np.diff(var_start))
+    elif x.shape != (B,):
+        raise ValueError(f"{what} must be a scalar, one value per variable ({V}) or one per level ({B})")
+    if not np.isfinite(x).all() or (x < lo).any():
+        raise ValueError(f"{what} must be finite and at least {lo}")
+    return np.ascontiguousarray(x)
+
+
+class _HarmonyState:
+    """The device tensors of a Harmony problem, and the stages on them."""
+
+    def __init__(self, Z, levels, var_start, K, device: int = 0):
+        self.ops = _harmony_ops(device)
+        tc = self.ops.torch
+        self.tc, self.dev = tc, tc.device("cuda", device)
+        self.N, self.d = Z.shape
+        self.K = int(K)
+        if levels is None:
+            levels, var_start = np.zeros((1, self.N), dtype=np.int32), np.array([0, 1], dtype=np.int32)
+        self.V, self.B, self.var_start = levels.shape[0], int(var_start[-1]), var_start
+        self.Z, self.levels = self.up(Z), self.up(levels)
+        self.ws = tc.zeros(self.ops.harmony_workspace_bytes(self.N, self.d, self.K, self.V, self.B), dtype=tc.uint8, device=self.dev)
+
+    def up(self, a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        return self.tc.from_numpy(a if a.flags.writeable else a.copy()).to(self.dev)
+
+    def f64(self, *shape):
+        return self.tc.zeros(shape, dtype=self.tc.float64, device=self.dev)
+
+    def sync(self):
+        return self.ops.harmony_sync(self.ws)
+
+
+def harmony_normalise(Z):
+    """Stage 1 of include/gficf_harmony.h alone: the rows of ``Z`` scaled to unit length (a zero row stays zero)."""
+    Z, _, _ = _harmony_check_shapes(Z, None, None)
+    s = _HarmonyState(Z, None, None, 1)
+    Zc = s.f64(s.N, s.d)
+    s.ops.harmony_normalise(s.Z, Zc, s.ws)
+    s.sync()
+    return Zc.cpu().numpy()
+
+
+def harmony_start(Zc, Y0, init_iter: int = 10) -> dict:
+    """Stage 2 alone: ``init_iter`` hard Lloyd iterations under cosine from the centroids ``Y0``: ``{"Y", "labels"}``."""
+    Y0 = np.ascontiguousarray(Y0, dtype=np.float64)
+    Zc, _, _ = _harmony_check_shapes(Zc, None, None, K=Y0.shape[0] if Y0.ndim == 2 else 0)
+    if Y0.ndim != 2 or Y0.shape[1] != Zc.shape[1]:
+        raise ValueError("Y0 must be K x d")
+    if init_iter < 0:
+        raise ValueError("init_iter must not be negative")
+    s = _HarmonyState(Zc, None, None, Y0.shape[0])
+    Y, lab = s.f64(s.K, s.d), s.tc.zeros(s.N, dtype=s.tc.int32, device=s.dev)
+    s.ops.harmony_start(s.up(Zc), s.up(Y0), int(init_iter), Y, lab, s.ws)
+    s.sync()
+    return {"Y": Y.cpu().numpy(), "labels": lab.cpu().numpy()}
+
+
+def _harmony_stage_args(Zc, levels, var_start, Y, sigma, R=None, O=None, E=None, theta=None):
+    """The arguments the stage mirrors share, checked before a device is touched."""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    Zc, levels, var_start = _harmony_check_shapes(Zc, levels, var_start, K=Y.shape[0] if Y.ndim == 2 else 0)
+    if levels is None:
+        raise ValueError("levels and var_start are needed")
+    if Y.ndim != 2 or Y.shape[1] != Zc.shape[1]:
+        raise ValueError("Y must be K x d")
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be positive and finite")
+    K, N, B = Y.shape[0], Zc.shape[0], int(var_start[-1])
+    roe = []
+    for a, shape, name in ((R, (K, N), "R"), (O, (K, B), "O"), (E, (K, B), "E")):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"{name} must be {shape[0]} x {shape[1]}")
+        roe.append(a)
+    if theta is not None:
+        theta = _harmony_per_level(theta, var_start, "theta")
+    return Zc, levels, var_start, Y, roe, theta
+
+
+def harmony_assign(Zc, levels, var_start, Y, sigma: float = 0.1) -> dict:
+    """Stage 3 alone: ``{"R", "O", "E"}`` of the centroids ``Y`` without penalty."""
+    Zc, levels, var_start, Y, _, _ = _harmony_stage_args(Zc, levels, var_start, Y, sigma)
+    s = _HarmonyState(Zc, levels, var_start, Y.shape[0])
+    R, O, E = s.f64(s.K, s.N), s.f64(s.K, s.B), s.f64(s.K, s.B)
+    s.ops.harmony_assign(s.Z, s.levels, s.var_start, s.up(Y), sigma, R, O, E, s.ws)
+    s.sync()
+    return {"R": R.cpu().numpy(), "O": O.cpu().numpy(), "E": E.cpu().numpy()}
+
+
+def harmony_round(Zc, levels, var_start, Y, R, O, E, theta, sigma, perm, n_blocks: int) -> dict:
+    """Stage 4 alone: one clustering round over the ``n_blocks`` blocks of the permutation ``perm``: ``{"R", "O", "E", "Y"}``."""
+    Zc, levels, var_start, Y, (R, O, E), theta = _harmony_stage_args(Zc, levels, var_start, Y, sigma, R, O, E, theta)
+    perm = np.ascontiguousarray(perm, dtype=np.int32)
+    if perm.shape != (Zc.shape[0],) or not np.array_equal(np.sort(perm), np.arange(Zc.shape[0])):
+        raise ValueError("perm must be a permutation of the cells")
+    if n_blocks < 1:
+        raise ValueError("n_blocks must be at least 1")
+    s = _HarmonyState(Zc, levels, var_start, Y.shape[0])
+    Rd, Od, Ed, Yd = s.up(R), s.up(O), s.up(E), s.up(Y)
+    s.ops.harmony_round(s.Z, s.levels, s.var_start, s.up(theta), sigma, s.up(perm), int(n_blocks), Rd, Od, Ed, Yd, s.ws)
+    s.sync()
+    return {"R": Rd.cpu().numpy(), "O": Od.cpu().numpy(), "E": Ed.cpu().numpy(), "Y": Yd.cpu().numpy()}
+
+
+def harmony_objective(Zc, levels, var_start, Y, R, O, E, theta, sigma: float = 0.1) -> float:
+    """Stage 5 alone: the objective of (Y, R, O, E)."""
+    Zc, levels, var_start, Y, (R, O, E), theta = _harmony_stage_args(Zc, levels, var_start, Y, sigma, R, O, E, theta)
+    s = _HarmonyState(Zc, levels, var_start, Y.shape[0])
+    obj = s.f64(1)
+    s.ops.harmony_objective(s.Z, s.levels, s.var_start, s.up(Y), s.up(R), s.up(O), s.up(E), s.up(theta), sigma, obj, s.ws)
+    s.sync()
+    return float(obj.cpu()[0])
+
+
+def harmony_correct(Z, levels, var_start, R, lamb=1.0) -> dict:
+    """Stage 6 alone: ``{"Z": the corrected cells, "W": (K, B + 1, d) ridge coefficients, "flat_clusters"}``."""
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    Z, levels, var_start = _harmony_check_shapes(Z, levels, var_start, K=R.shape[0] if R.ndim == 2 else 0)
+    if levels is None:
+        raise ValueError("levels and var_start are needed")
+    if R.ndim != 2 or R.shape[1] != Z.shape[0]:
+        raise ValueError("R must be K x N")
+    lamb = _harmony_per_level(lamb, var_start, "lamb")
+    s = _HarmonyState(Z, levels, var_start, R.shape[0])
+    Zcorr, W = s.f64(s.N, s.d), s.f64(s.K, s.B + 1, s.d)
+    s.ops.harmony_correct(s.Z, s.levels, s.var_start, s.up(R), s.up(lamb), Zcorr, s.ws, W)
+    info = s.sync()
+    return {"Z": Zcorr.cpu().numpy(), "W": W.cpu().numpy(), "flat_clusters": info["flat_clusters"]}
+
+
+def _harmony_setup(X, batch, theta, lamb, sigma, nclust, tau, block_size, max_iter_harmony, max_iter_kmeans, epsilon_cluster, epsilon_harmony,
+                   init_iter):
+    """The argument checks of :func:`harmony_matrix`, and what it derives on the host."""
+    X, _, _ = _harmony_check_shapes(X, None, None)
+    N = X.shape[0]
+    levels, var_start, names, labels = harmony_levels(batch, N)
+    K = min(int(round(N / 30.0)), 100) if nclust is None else int(nclust)
+    K = max(K, 1) if nclust is None else K
+    _harmony_check_shapes(X, levels, var_start, K=K)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be positive and finite")
+    if not 0 < block_size <= 1:
+        raise ValueError("block_size must be in (0, 1]")
+    if min(max_iter_harmony, max_iter_kmeans, init_iter) < 0:
+        raise ValueError("the iteration limits must not be negative")
+    if tau < 0:
+        raise ValueError("tau must not be negative")
+    theta = _harmony_per_level(theta, var_start, "theta")
+    lamb = _harmony_per_level(lamb, var_start, "lamb")
+    if tau > 0:
+        counts = np.stack([(levels == b).sum() for b in range(int(var_start[-1]))]).astype(np.float64)
+        theta = theta * (1.0 - np.exp(-(counts / (K * tau)) ** 2))
+    return dict(X=X, levels=levels, var_start=var_start, names=names, labels=labels, K=K, theta=theta, lamb=lamb, sigma=float(sigma),
+                n_blocks=int(np.ceil(1.0 / block_size)), max_iter_harmony=int(max_iter_harmony), max_iter_kmeans=int(max_iter_kmeans),
+                epsilon_cluster=float(epsilon_cluster), epsilon_harmony=float(epsilon_harmony), init_iter=int(init_iter))
+
+
+def harmony_matrix(X, batch, theta=2.0, lamb=1.0, sigma: float = 0.1, nclust: int | None = None, tau: float = 0.0, block_size: float = 0.05,
+                   max_iter_harmony: int = 10, max_iter_kmeans: int = 20, epsilon_cluster: float = 1e-5, epsilon_harmony: float = 1e-4,
+                   seed: int = 180582, init_iter: int = 10) -> dict:
+    """Harmony (Korsunsky et al. 2019) of the N x d cells ``X`` for the batch variable(s) ``batch``, on the device: the chain of
+    include/gficf_harmony.h (``gficf_harmony_device``).  Returns ``Z`` (the corrected cells), ``R`` (K x N soft assignments), ``Y``
+    (K x d centroids), ``objective`` (the last objective of every outer iteration), ``objective_rounds`` (every round's, the
+    start's first), ``iter_rounds``, ``iterations``, ``rounds``, ``converged``, ``levels`` (per variable, its labels in order of
+    first appearance), ``flat_clusters`` (clusters the last correction left out) and ``last_change`` (the last relative drop).
+
+    ``nclust=None``: ``min(round(N / 30), 100)``, at least 1.  ``theta`` and ``lamb``: a scalar, or one value per variable (or per
+    level).  ``tau > 0`` scales ``theta[b]`` by ``1 - exp(-(N_b / (K tau))^2)``.  The random inputs are those of
+    :func:`harmony_draws` with ``seed``: the start centroids are the drawn cells, normalised."""
+    p = _harmony_setup(X, batch, theta, lamb, sigma, nclust, tau, block_size, max_iter_harmony, max_iter_kmeans, epsilon_cluster, epsilon_harmony,
+                       init_iter)
+    X, K = p["X"], p["K"]
+    N = X.shape[0]
+    cells, perm = harmony_draws(N, K, p["max_iter_harmony"] * p["max_iter_kmeans"], seed)
+    s = _HarmonyState(X, p["levels"], p["var_start"], K)
+    Y0 = s.up(X[cells])
+    s.ops.harmony_normalise(Y0, Y0, s.ws)
+    Zcorr, Zc, R, Y, O, E = s.f64(s.N, s.d), s.f64(s.N, s.d), s.f64(K, s.N), s.f64(K, s.d), s.f64(K, s.B), s.f64(K, s.B)
+    permd = s.up(perm) if perm.shape[0] else s.tc.zeros((0, N), dtype=s.tc.int32, device=s.dev)
+    out = s.ops.harmony(s.Z, s.levels, s.var_start, s.up(p["theta"]), s.up(p["lamb"]), p["sigma"], Y0, permd, p["init_iter"], p["max_iter_harmony"],
+                        p["max_iter_kmeans"], p["n_blocks"], p["epsilon_cluster"], p["epsilon_harmony"], Zcorr, Zc, R, Y, O, E, s.ws)
+    info = s.sync()
+    ends = np.cumsum(out["iter_rounds"])
+    h = out["objective"][ends]
+    last = float((h[-2] - h[-1]) / abs(h[-2])) if len(h) >= 2 else float("nan")
+    return {"Z": Zcorr.cpu().numpy(), "R": R.cpu().numpy(), "Y": Y.cpu().numpy(), "objective": h, "objective_rounds": out["objective"],
+            "iter_rounds": out["iter_rounds"], "iterations": out["iterations"], "rounds": out["rounds"], "converged": out["converged"],
+            "levels": dict(zip(p["names"], p["labels"])), "flat_clusters": info["flat_clusters"], "zero_rows": info["zero_rows"],
+            "last_change": last, "nclust": K, "theta": p["theta"], "lamb": p["lamb"], "n_blocks": p["n_blocks"]}
+
+
+def runHarmony(data: dict, batch, theta=2.0, lamb=1.0, sigma: float = 0.1, nclust: int | None = None, tau: float = 0.0, block_size: float = 0.05,
+               max_iter_harmony: int = 10, max_iter_kmeans: int = 20, epsilon_cluster: float = 1e-5, epsilon_harmony: float = 1e-4,
+               seed: int = 180582) -> dict:
+    """Harmony batch correction of ``data["pca"]["cells"]`` between :func:`runPCA` and :func:`runReduction` / :func:`clustcells`
+    (the reference's later releases add ``runHarmony`` at this place): see :func:`harmony_matrix`.  ``data["pca"]["cells"]`` becomes
+    the corrected matrix, ``data["pca"]["cells_uncorrected"]`` keeps the original (a second call starts from it again) and
+    ``data["pca"]["harmony"]`` holds the parameters, ``iterations``, ``objective`` and ``converged``.  New cells are not corrected:
+    :func:`embedNewCells` and ``classify_cells(method="PCA")`` refuse a ``data`` that carries ``data["pca"]["harmony"]``."""
+    if data.get("pca") is None:
+        raise ValueError("First run runPCA or runLSA to reduce dimensionality")
+    pca = data["pca"]
+    orig = np.asarray(pca["cells_uncorrected"] if pca.get("cells_uncorrected") is not None else pca["cells"], dtype=np.float64)
+    r = harmony_matrix(orig, batch, theta, lamb, sigma, nclust, tau, block_size, max_iter_harmony, max_iter_kmeans, epsilon_cluster, epsilon_harmony, seed)
+    if not r["converged"]:
+        warnings.warn(f"runHarmony did not converge in {max_iter_harmony} iterations: the last relative change of the objective was "
+                      f"{r['last_change']:.3g} (epsilon_harmony = {epsilon_harmony:g})")
+    pca["cells_uncorrected"] = orig
+    pca["cells"] = r["Z"]
+    pca["harmony"] = {"theta": r["theta"], "lamb": r["lamb"], "sigma": float(sigma), "nclust": r["nclust"], "tau": float(tau),
+                      "block_size": float(block_size), "max_iter_harmony": int(max_iter_harmony), "max_iter_kmeans": int(max_iter_kmeans),
+                      "epsilon_cluster": float(epsilon_cluster), "epsilon_harmony": float(epsilon_harmony), "seed": int(seed),
+                      "levels": r["levels"], "iterations": r["iterations"], "rounds": r["rounds"], "objective": r["objective"],
+                      "converged": r["converged"], "flat_clusters": r["flat_clusters"]}
+    return data
+
+
+def _refuse_after_harmony(data: dict, what: str):
+    if isinstance(data.get("pca"), dict) and data["pca"].get("harmony") is not None:
+        raise NotImplementedError(f"{what} after runHarmony is not provided: new cells are not batch corrected, so they cannot be placed among "
+                                  "the corrected data['pca']['cells']")
 
 
 # ----------------------------------------------------------- device-resident stage ops
@@ -4161,6 +4471,102 @@ class HipOps:
         from . import _hvg_lib
 
         check(_hvg_lib.load().gficf_hvg_sync(self._bind(), _tptr(ws)))
+
+    # -- Harmony (libgficf_harmony.so, include/gficf_harmony.h); all tensors float64 but ``levels``, ``perm``, ``labels`` (int32):
+    # Z, Zc, Zcorr (N, d); levels (V, N); Y (K, d); R (K, N); O, E (K, B); theta, lamb (B,); ``var_start`` is a host int32 array
+    # of V + 1; ``ws``: uint8 of ``harmony_workspace_bytes``.  Every stage only enqueues; ``harmony`` waits once a round for the
+    # objective; ``harmony_sync(ws)`` waits and collects the deferred errors.
+    @staticmethod
+    def harmony_workspace_bytes(N: int, d: int, K: int, V: int, B: int) -> int:
+        from . import _harmony_lib
+
+        return int(_harmony_lib.load().gficf_harmony_workspace_bytes(int(N), int(d), int(K), int(V), int(B)))
+
+    @staticmethod
+    def _harmony_dims(Z, Y, levels, var_start):
+        vs = np.ascontiguousarray(var_start, dtype=np.int32)
+        V = int(levels.shape[0])
+        if vs.shape != (V + 1,):
+            raise ValueError("var_start must hold one entry per variable and the total")
+        return int(Z.shape[0]), int(Z.shape[1]), int(Y.shape[0]), V, int(vs[-1]), vs
+
+    def harmony_normalise(self, Z, Zc, ws):
+        """Stage 1: ``Zc[i] = Z[i] / |Z[i]|``; starts the status word and the counters of ``ws`` again."""
+        from . import _harmony_lib
+
+        check(_harmony_lib.load().gficf_harmony_normalise_device(self._bind(), int(Z.shape[0]), int(Z.shape[1]), _tptr(Z), _tptr(Zc), _tptr(ws),
+                                                                 int(ws.numel())))
+
+    def harmony_start(self, Zc, Y0, init_iter, Y, labels, ws):
+        """Stage 2: ``init_iter`` hard Lloyd iterations under cosine from ``Y0``."""
+        from . import _harmony_lib
+
+        check(_harmony_lib.load().gficf_harmony_start_device(self._bind(), int(Zc.shape[0]), int(Zc.shape[1]), int(Y0.shape[0]), _tptr(Zc), _tptr(Y0),
+                                                             int(init_iter), _tptr(Y), _tptr(labels), _tptr(ws), int(ws.numel())))
+
+    def harmony_assign(self, Zc, levels, var_start, Y, sigma, R, O, E, ws):
+        """Stage 3: the soft assignments of ``Y`` without penalty, ``O = R Phi^T`` and ``E``."""
+        from . import _harmony_lib
+
+        N, d, K, V, B, vs = self._harmony_dims(Zc, Y, levels, var_start)
+        check(_harmony_lib.load().gficf_harmony_assign_device(self._bind(), N, d, K, V, B, _np_ptr(vs), _tptr(Zc), _tptr(levels), _tptr(Y), float(sigma),
+                                                              _tptr(R), _tptr(O), _tptr(E), _tptr(ws), int(ws.numel())))
+
+    def harmony_round(self, Zc, levels, var_start, theta, sigma, perm, n_blocks, R, O, E, Y, ws):
+        """Stage 4: one clustering round over the blocks of ``perm`` (N int32); R, O, E and Y are updated in place."""
+        from . import _harmony_lib
+
+        N, d, K, V, B, vs = self._harmony_dims(Zc, Y, levels, var_start)
+        if perm.numel() != N:
+            raise ValueError("perm must hold N entries")
+        check(_harmony_lib.load().gficf_harmony_round_device(self._bind(), N, d, K, V, B, _np_ptr(vs), _tptr(Zc), _tptr(levels), _tptr(theta), float(sigma),
+                                                             _tptr(perm), int(n_blocks), _tptr(R), _tptr(O), _tptr(E), _tptr(Y), _tptr(ws),
+                                                             int(ws.numel())))
+
+    def harmony_objective(self, Zc, levels, var_start, Y, R, O, E, theta, sigma, obj, ws):
+        """Stage 5: the objective into ``obj`` (float64 of 1, on the device)."""
+        from . import _harmony_lib
+
+        N, d, K, V, B, vs = self._harmony_dims(Zc, Y, levels, var_start)
+        check(_harmony_lib.load().gficf_harmony_objective_device(self._bind(), N, d, K, V, B, _np_ptr(vs), _tptr(Zc), _tptr(levels), _tptr(Y), _tptr(R),
+                                                                 _tptr(O), _tptr(E), _tptr(theta), float(sigma), _tptr(obj), _tptr(ws), int(ws.numel())))
+
+    def harmony_correct(self, Z, levels, var_start, R, lamb, Zcorr, ws, W=None):
+        """Stage 6: ``Zcorr`` from the original ``Z``; ``W`` (K, B + 1, d), if given, gets the ridge coefficients."""
+        from . import _harmony_lib
+
+        N, d, K, V, B, vs = self._harmony_dims(Z, R, levels, var_start)
+        check(_harmony_lib.load().gficf_harmony_correct_device(self._bind(), N, d, K, V, B, _np_ptr(vs), _tptr(Z), _tptr(levels), _tptr(R), _tptr(lamb),
+                                                               _tptr(Zcorr), _tptr(W), _tptr(ws), int(ws.numel())))
+
+    def harmony(self, Z, levels, var_start, theta, lamb, sigma, Y0, perm, init_iter, max_iter_harmony, max_iter_kmeans, n_blocks, epsilon_cluster,
+                epsilon_harmony, Zcorr, Zc, R, Y, O, E, ws) -> dict:
+        """Stage 7, the chain; ``perm`` (rounds, N) int32.  Returns ``objective`` (every round's, the one after stage 3 first),
+        ``iter_rounds``, ``iterations``, ``rounds`` and ``converged``."""
+        from . import _harmony_lib
+
+        N, d, K, V, B, vs = self._harmony_dims(Z, Y0, levels, var_start)
+        rounds = int(perm.shape[0]) if perm.dim() == 2 else 0
+        if rounds and int(perm.shape[1]) != N:
+            raise ValueError("perm must be (rounds, N)")
+        objective = np.full(rounds + 1, np.nan, dtype=np.float64)
+        iter_rounds = np.zeros(max(int(max_iter_harmony), 1), dtype=np.int32)
+        info = np.zeros(4, dtype=np.int64)
+        check(_harmony_lib.load().gficf_harmony_device(self._bind(), N, d, K, V, B, _np_ptr(vs), _tptr(Z), _tptr(levels), _tptr(theta), _tptr(lamb),
+                                                       float(sigma), _tptr(Y0), _tptr(perm), rounds, int(init_iter), int(max_iter_harmony),
+                                                       int(max_iter_kmeans), int(n_blocks), float(epsilon_cluster), float(epsilon_harmony), _tptr(Zcorr),
+                                                       _tptr(Zc), _tptr(R), _tptr(Y), _tptr(O), _tptr(E), _np_ptr(objective), _np_ptr(iter_rounds),
+                                                       _np_ptr(info), _tptr(ws), int(ws.numel())))
+        return {"objective": objective[:1 + int(info[1])], "iter_rounds": iter_rounds[:int(info[0])], "iterations": int(info[0]),
+                "rounds": int(info[1]), "converged": bool(info[2])}
+
+    def harmony_sync(self, ws) -> dict:
+        """Waits; raises the deferred errors; returns ``zero_rows`` and ``flat_clusters`` of the last normalisation and correction."""
+        from . import _harmony_lib
+
+        info = np.zeros(2, dtype=np.int64)
+        check(_harmony_lib.load().gficf_harmony_sync(self._bind(), _tptr(ws), _np_ptr(info)))
+        return {"zero_rows": int(info[0]), "flat_clusters": int(info[1])}
 
     # -- overdispersed genes (libgficf_od.so); ``ws``: uint8 of ``od_workspace_bytes``, its first word zero before the first stage
     # (``torch.zeros``); ``od_fit`` and ``od_bh_log`` wait once for their host stage, the others only enqueue; ``od_sync(ws)``
