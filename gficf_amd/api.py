@@ -1836,6 +1836,270 @@ def svds(A_csc_genes_x_cells, k: int, centre: bool = False, tol: float = 1e-10, 
             "cycles": int(info[0]), "products": int(info[1]), "exhausted": exhausted}
 
 
+# ------------------------------------------------------------------ NMF (libgficf_nmf.so)
+NMF_MAX_K = 128
+_NMF_OPS: dict = {}
+
+
+def _nmf_ops(device: int = 0):
+    """The stage object the NMF mirrors enqueue on (one per device, made at the first call)."""
+    if device not in _NMF_OPS:
+        _NMF_OPS[device] = HipOps(device)
+    return _NMF_OPS[device]
+
+
+def _nmf_pad(X, k: int, name: str, rows=None) -> np.ndarray:
+    """``X`` (rows x k) as the library holds it: row-major float64 with the pitch ``_nmf_lib.ld(k)``, the padding zero."""
+    from . import _nmf_lib
+
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != k or (rows is not None and X.shape[0] != rows):
+        raise ValueError(f"{name} must be {'a matrix' if rows is None else rows} x {k}, not {X.shape}")
+    out = np.zeros((X.shape[0], _nmf_lib.ld(k)), dtype=np.float64)
+    out[:, :k] = X
+    return out
+
+
+def _nmf_limits(cd_tol, cd_maxit, ridge=0.0):
+    if not (cd_tol >= 0 and ridge >= 0) or int(cd_maxit) < 0:
+        raise ValueError("cd_tol, cd_maxit and ridge may not be negative")
+
+
+def _nmf_matrix(A, name="A"):
+    M, colptr, rowidx, x = _csc_parts(A)
+    if len(x) and not (x.min() >= 0):
+        raise ValueError(f"{name} holds a negative (or NaN) entry: the factorisation is of non-negative data")
+    return M, colptr, rowidx, x
+
+
+def _nmf_k(k, n: int) -> int:
+    k = int(k)
+    if not 1 <= k <= min(NMF_MAX_K, n):
+        raise ValueError(f"k = {k}: 1 <= k <= min({NMF_MAX_K}, G, N) = {min(NMF_MAX_K, n)} is required")
+    return k
+
+
+class _NmfState:
+    """The device tensors of one sparse matrix (n_in rows, n_out columns) and a workspace for k factors."""
+
+    def __init__(self, A, k: int, device: int = 0):
+        self.ops = _nmf_ops(device)
+        tc = self.ops.torch
+        self.tc, self.dev, self.k = tc, tc.device("cuda", device), int(k)
+        M, colptr, rowidx, x = _nmf_matrix(A)
+        self.n_in, self.n_out = M.shape
+        self.colptr, self.rowidx, self.x = self.up(colptr.astype(np.int64)), self.up(rowidx), self.up(x)
+        self.ws = tc.zeros(self.ops.nmf_workspace_bytes(self.n_in, self.n_out, len(x), self.k), dtype=tc.uint8, device=self.dev)
+
+    def up(self, a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        if a.size == 0:
+            a = np.zeros(1, dtype=a.dtype)
+        return self.tc.from_numpy(a if a.flags.writeable else a.copy()).to(self.dev)
+
+    def zeros(self, *shape, dtype=None):
+        return self.tc.zeros(shape, dtype=dtype or self.tc.float64, device=self.dev)
+
+
+def nnls(S, B, H0=None, cd_tol: float = 1e-8, cd_maxit: int = 100, ret_sweeps: bool = False, device: int = 0):
+    """The batched non-negative least-squares solve of include/gficf_nmf.h: for every row ``b`` of ``B`` (M x k) the ``h >= 0``
+    that minimises ``h'S h / 2 - b'h`` (``S``: k x k), by cyclic coordinate descent in a fixed order, started from ``H0``
+    (M x k, non-negative) or from zero.  Returns ``H`` (M x k), with ``ret_sweeps`` also the sweeps every row took (int32)."""
+    from . import _nmf_lib
+
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1] or not 1 <= S.shape[0] <= NMF_MAX_K:
+        raise ValueError(f"S must be k x k with 1 <= k <= {NMF_MAX_K}")
+    k = S.shape[0]
+    _nmf_limits(cd_tol, cd_maxit)
+    Bp = _nmf_pad(B, k, "B")
+    M = Bp.shape[0]
+    if M < 1:
+        raise ValueError("B must have a row")
+    H0p = None if H0 is None else _nmf_pad(H0, k, "H0", rows=M)
+    if H0p is not None and not (H0p.min() >= 0):
+        raise ValueError("H0 holds a negative (or NaN) entry")
+    ops = _nmf_ops(device)
+    tc, dev = ops.torch, ops.torch.device("cuda", device)
+    H = tc.zeros((M, _nmf_lib.ld(k)), dtype=tc.float64, device=dev)
+    sweeps = tc.zeros(M, dtype=tc.int32, device=dev)
+    ws = tc.zeros(_nmf_lib.NNLS_WS_BYTES, dtype=tc.uint8, device=dev)
+    ops.nnls(k, tc.from_numpy(S).to(dev), tc.from_numpy(Bp).to(dev), None if H0p is None else tc.from_numpy(H0p).to(dev), cd_tol, cd_maxit, H, sweeps, ws)
+    ops.nmf_sync(ws)
+    H = H.cpu().numpy()[:, :k].copy()
+    return (H, sweeps.cpu().numpy()) if ret_sweeps else H
+
+
+def nmf_half(A, X, Y=None, d=None, l1: float = 0.0, ridge: float = 1e-15, cd_tol: float = 1e-8, cd_maxit: int = 100, device: int = 0) -> dict:
+    """One half-step of :func:`nmf` alone (steps 1 - 3 of include/gficf_nmf.h) on the sparse ``A`` (n_in x n_out): from the factor
+    ``X`` (n_in x k) to the normalised factor ``y`` (n_out x k) and the scaling ``d``.  With ``Y`` and ``d`` (the previous
+    factor and scaling) the solve starts from their product.  Also returned: ``S`` (k x k) and ``B`` (n_out x k) as the device
+    formed them, ``sweeps`` per row, ``dead`` factors and ``capped`` rows."""
+    from . import _nmf_lib
+
+    X = np.asarray(X, dtype=np.float64)
+    k = X.shape[1] if X.ndim == 2 else 0
+    if not 1 <= k <= NMF_MAX_K:
+        raise ValueError(f"X must be n_in x k with 1 <= k <= {NMF_MAX_K}")
+    _nmf_limits(cd_tol, cd_maxit, ridge)
+    s = _NmfState(A, k, device)
+    tc, ldk, lpk = s.tc, _nmf_lib.ld(k), _nmf_lib.lp(k)
+    Xd = s.up(_nmf_pad(X, k, "X", rows=s.n_in))
+    warm = Y is not None
+    if warm and d is None:
+        raise ValueError("a warm start needs both Y and d")
+    Yd = s.up(_nmf_pad(Y, k, "Y", rows=s.n_out)) if warm else s.zeros(s.n_out, ldk)
+    dd = s.up(np.ascontiguousarray(d, dtype=np.float64).reshape(k)) if warm else s.zeros(k)
+    S, B = s.zeros(lpk, lpk), s.zeros(s.n_out, ldk)
+    sweeps, counts = s.zeros(s.n_out, dtype=tc.int32), s.zeros(2, dtype=tc.int64)
+    s.ops.nmf_half(s.n_in, s.n_out, s.colptr, s.rowidx, s.x, len(_csc_parts(A)[3]), k, Xd, Yd, dd, warm, l1, ridge, cd_tol, cd_maxit, s.ws, S=S, B=B,
+                   sweeps=sweeps, counts=counts)
+    s.ops.nmf_sync(s.ws)
+    counts = counts.cpu().numpy()
+    return {"y": Yd.cpu().numpy()[:, :k].copy(), "d": dd.cpu().numpy(), "S": S.cpu().numpy()[:k, :k].copy(), "B": B.cpu().numpy()[:, :k].copy(),
+            "sweeps": sweeps.cpu().numpy(), "dead": int(counts[0]), "capped": int(counts[1])}
+
+
+def nmf_loss(A, w, d, h, device: int = 0, ret_terms: bool = False):
+    """``||A - w diag(d) h||_F^2`` for the sparse ``A`` (G x N), ``w`` (G x k), ``d`` (k) and ``h`` (k x N), without densifying
+    (include/gficf_nmf.h): ``||A||^2`` minus twice the cross term plus the quadratic term, which cancel once the fit is good,
+    so its last digits mean nothing then.  ``ret_terms``: the four numbers ``(loss, ||A||^2, cross, quad)``."""
+    w, h = np.asarray(w, dtype=np.float64), np.asarray(h, dtype=np.float64)
+    k = w.shape[1] if w.ndim == 2 else 0
+    if not 1 <= k <= NMF_MAX_K:
+        raise ValueError(f"w must be G x k with 1 <= k <= {NMF_MAX_K}")
+    s = _NmfState(A, k, device)
+    if h.ndim != 2 or h.shape != (k, s.n_out):
+        raise ValueError(f"h must be k x N = {k} x {s.n_out}, not {h.shape}")
+    out = s.zeros(4)
+    s.ops.nmf_loss(s.n_in, s.n_out, s.colptr, s.rowidx, s.x, len(_csc_parts(A)[3]), k, s.up(_nmf_pad(w, k, "w", rows=s.n_in)),
+                   s.up(np.ascontiguousarray(d, dtype=np.float64).reshape(k)), s.up(_nmf_pad(h.T, k, "h")), out, s.ws)
+    s.ops.nmf_sync(s.ws)
+    out = out.cpu().numpy()
+    return tuple(out) if ret_terms else float(out[0])
+
+
+def nmf(A, k: int, seed: int = 180582, W0=None, tol: float = 1e-4, maxit: int = 100, L1=(0.0, 0.0), cd_tol: float = 1e-8, cd_maxit: int = 100,
+        ridge: float = 1e-15, track_loss: bool = False, ctx: Context | None = None) -> dict:
+    """Non-negative matrix factorisation ``A ~ w diag(d) h`` of the genes x cells matrix ``A`` (scipy CSC, non-negative) by
+    alternating non-negative least squares on the device.  The contract is the method of include/gficf_nmf.h, not RcppML's or
+    scikit-learn's bits: the start ``W0`` (G x k, non-negative) is drawn here, ``np.random.default_rng(seed).random((G, k))``,
+    unless given (the library holds no generator); every solve is cyclic coordinate descent in one fixed order, stopped by a
+    maximum (``cd_tol``, ``cd_maxit``); the iteration stops when ``1 - cor(w, w_previous) < tol`` or after ``maxit``
+    iterations; ``L1 = (L1_w, L1_h)`` is subtracted from the right-hand sides; no masking, no symmetric shortcut.
+
+    Returns ``w`` (G x k, columns sum to 1), ``d`` (k), ``h`` (k x N, rows sum to 1), ``cells`` = ``(diag(d) h)'`` (N x k, so that
+    ``A ~ w cells'``, as ``runLSA`` has ``cells = u diag(d)``), ``iterations``, ``delta`` (one per iteration), ``converged``
+    (``tol`` stopped it), ``loss`` (one per iteration with ``track_loss``, else None), ``dead`` (factors whose scaling fell to
+    zero: they stay zero, never NaN) and ``capped_rows`` (rows of the last iteration whose solve ended at ``cd_maxit``).  A run
+    that reaches ``maxit`` warns and names the last ``delta``; the same input gives the same bits on every call."""
+    from . import _nmf_lib
+
+    M, colptr, rowidx, x = _nmf_matrix(A)
+    G, N = M.shape
+    k = _nmf_k(k, min(G, N))
+    L1 = tuple(float(v) for v in np.broadcast_to(np.asarray(L1, dtype=np.float64), (2,)))
+    _nmf_limits(cd_tol, cd_maxit, ridge)
+    if not (tol >= 0 and L1[0] >= 0 and L1[1] >= 0) or int(maxit) < 0:
+        raise ValueError("tol, maxit and L1 may not be negative")
+    if W0 is None:
+        W0 = np.random.default_rng(seed).random((G, k))
+    W0 = np.ascontiguousarray(W0, dtype=np.float64)
+    if W0.shape != (G, k):
+        raise ValueError(f"W0 must be G x k = {G} x {k}, not {W0.shape}")
+    if not (W0.min() >= 0):
+        raise ValueError("W0 holds a negative (or NaN) entry")
+    maxit = int(maxit)
+    w, d, h = np.zeros((G, k)), np.zeros(k), np.zeros((N, k))
+    delta, loss, info = np.full(max(maxit, 1), np.nan), np.full(max(maxit, 1), np.nan), np.zeros(4, dtype=np.int64)
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_nmf_lib.load().gficf_nmf_host(ctx.handle, G, N, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), k, _np_ptr(W0), float(tol), maxit,
+                                         L1[0], L1[1], float(ridge), float(cd_tol), int(cd_maxit), 1 if track_loss else 0, _np_ptr(w), _np_ptr(d),
+                                         _np_ptr(h), _np_ptr(delta), _np_ptr(loss), _np_ptr(info)))
+    it, converged = int(info[0]), bool(info[1])
+    if not converged and maxit > 0:
+        warnings.warn(f"nmf: stopped after maxit = {maxit} iterations with delta = {delta[it - 1]:.3g} >= tol = {tol:g}; raise maxit or tol",
+                      stacklevel=2)
+    return {"w": w, "d": d, "h": np.ascontiguousarray(h.T), "cells": h * d, "iterations": it, "delta": delta[:it], "converged": converged,
+            "loss": loss[:it] if track_loss else None, "dead": int(info[2]), "capped_rows": int(info[3]), "tol": float(tol), "seed": int(seed)}
+
+
+def _pca_new_rows(data: dict, gficf_new, ctx):
+    """The rows of ``gficf_new`` that ``data["pca"]`` decomposed (``gene_rows``), scaled by the stored ``gsf`` with ``rescale``."""
+    if data["pca"].get("gene_rows") is None:
+        return gficf_new
+    od = data["pca"]["odgenes"]
+    G_all = len(od["gsf"])
+    if gficf_new.shape[0] != G_all:
+        raise ValueError("gficf_new must have one row per row of data['gficf'] (data['pca']['odgenes'])")
+    rows = np.asarray(data["pca"]["gene_rows"], dtype=np.int64)
+    scale = np.ascontiguousarray(od["gsf"], dtype=np.float64) if data["pca"].get("rescale") else None
+    every = len(rows) == G_all
+    if scale is not None or not every:
+        gficf_new = select_scale_rows(gficf_new, None if every else rows, scale, ctx)
+    return gficf_new
+
+
+def nmf_project(data_or_w, gficf_new, ridge=None, cd_tol=None, cd_maxit=None, ret_sweeps: bool = False, ctx: Context | None = None):
+    """New cells against a trained NMF: ``data_or_w`` is the ``data`` of :func:`runNMF` or a ``w`` (G x k), ``gficf_new`` the
+    genes x new-cells GF-ICF matrix over the same genes.  Every new cell ``a`` gets the ``c >= 0`` that minimises
+    ``||a - w c||`` (``S = w'w + ridge``, ``B = gficf_new' w``, :func:`nnls` from zero): n_new x k, in the units of the
+    training ``cells``.  The limits default to those of the training run (``data["pca"]["nmf"]``) or of :func:`nmf`."""
+    from . import _nmf_lib
+
+    kw = {"ridge": 1e-15, "cd_tol": 1e-8, "cd_maxit": 100}
+    if isinstance(data_or_w, dict):
+        pca = data_or_w.get("pca")
+        if pca is None or pca.get("type") != "NMF":
+            raise ValueError("First run runNMF")
+        gficf_new = _pca_new_rows(data_or_w, gficf_new, ctx)
+        w = pca["genes"]
+        kw.update({n: pca["nmf"][n] for n in kw if n in pca.get("nmf", {})})
+    else:
+        w = data_or_w
+    kw.update({n: v for n, v in (("ridge", ridge), ("cd_tol", cd_tol), ("cd_maxit", cd_maxit)) if v is not None})
+    _nmf_limits(kw["cd_tol"], kw["cd_maxit"], kw["ridge"])
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    M, colptr, rowidx, x = _nmf_matrix(gficf_new, "gficf_new")
+    G, n_new = M.shape
+    if w.ndim != 2 or w.shape[0] != G or not 1 <= w.shape[1] <= NMF_MAX_K:
+        raise ValueError("gficf_new must have one row per row of w (data['pca']['genes']), and w at most 128 columns")
+    k = w.shape[1]
+    h, sweeps = np.zeros((n_new, k)), np.zeros(n_new, dtype=np.int32)
+    ctx = ctx or default_context()
+    is64 = 1 if colptr.dtype == np.int64 else 0
+    check(_nmf_lib.load().gficf_nmf_project_host(ctx.handle, G, n_new, _np_ptr(colptr), is64, _np_ptr(rowidx), _np_ptr(x), k, _np_ptr(w),
+                                                 float(kw["ridge"]), float(kw["cd_tol"]), int(kw["cd_maxit"]), _np_ptr(h), _np_ptr(sweeps)))
+    return (h, sweeps) if ret_sweeps else h
+
+
+def runNMF(data: dict, dim=None, seed: int = 180582, use_odgenes=False, n_odgenes=None, var_scale=False, ctx: Context | None = None,
+           **nmf_kw) -> dict:
+    """Non-negative matrix factorisation of ``data["gficf"]`` (:func:`nmf`; ``nmf_kw``: its ``tol``, ``maxit``, ``L1``, ``cd_tol``,
+    ``cd_maxit``, ``ridge``, ``track_loss``, ``W0``) where :func:`runPCA` / :func:`runLSA` take a signed SVD: parts-based,
+    non-negative gene programmes.  The reference has no such step; it sits where people put it, between ``gficf()`` and
+    ``clustcells()``.  Gene selection is :func:`runPCA`'s (``use_odgenes="cr"`` / ``var_scale="cr"``; ``True`` is refused as
+    there).  ``data["pca"]`` becomes ``{"cells": N x dim = (diag(d) h)', "genes": w (G x dim), "d", "h", "type": "NMF",
+    "centre": False, "rescale", "mean": None, "nmf": {iterations, delta, converged, loss, dead, ...}}`` plus ``"odgenes"`` /
+    ``"gene_rows"`` where used, so ``clustcells``, ``runReduction``, ``runTsne`` and ``runHarmony`` work on it unchanged, and
+    :func:`pca_project` (``embedNewCells``, ``classify_cells(method="PCA")``) places new cells by :func:`nmf_project`."""
+    if use_odgenes and data.get("rawCounts") is None:
+        raise ValueError(_RAW_ABSENT)
+    dim = _pca_dim(data, dim)
+    _pca_unsupported(var_scale, use_odgenes, True)
+    M, extra = _pca_matrix(data, var_scale, use_odgenes, n_odgenes, False, ctx)
+    r = nmf(M, dim, seed=seed, ctx=ctx, **nmf_kw)
+    how = {n: r[n] for n in ("iterations", "delta", "converged", "loss", "dead", "capped_rows", "tol", "seed")}
+    how.update({"ridge": float(nmf_kw.get("ridge", 1e-15)), "cd_tol": float(nmf_kw.get("cd_tol", 1e-8)), "cd_maxit": int(nmf_kw.get("cd_maxit", 100))})
+    data["pca"] = {"cells": r["cells"], "genes": r["w"], "d": r["d"], "h": r["h"], "type": "NMF", "centre": False, "rescale": bool(var_scale),
+                   "mean": None, "nmf": how}
+    data["pca"].update(extra)
+    return data
+
+
 # ------------------------------------------------------------------ overdispersed genes (libgficf_od.so)
 _OD_COLUMNS = ("v", "fit", "res", "lp", "lpa", "qv", "gsf")
 _RAW_ABSENT = "Raw Counts absent! Please run gficf normalization with storeRaw = T"
@@ -2221,21 +2485,15 @@ def pca_project(data: dict, gficf_new, ctx: Context | None = None) -> np.ndarray
     space, n_new x dim.  After ``runPCA(centre=True)`` the training gene means are subtracted first (the reference's
     ``scaleMatrix`` is a stub that does nothing).  After ``use_odgenes="cr"`` / ``var_scale="cr"`` (``data["pca"]["gene_rows"]``)
     ``gficf_new`` has one row per row of ``data["gficf"]``: the rows decomposed are selected and, with ``rescale``, scaled by
-    the stored ``gsf`` first (:func:`select_scale_rows`; reference R/cellClassifier.R:56-62)."""
+    the stored ``gsf`` first (:func:`select_scale_rows`; reference R/cellClassifier.R:56-62).  After :func:`runNMF`
+    (``data["pca"]["type"] == "NMF"``) the new cells are placed by the non-negative projection :func:`nmf_project` instead."""
     from . import _pca_lib
 
     if data.get("pca") is None:
         raise ValueError("First run runPCA or runLSA to reduce dimensionality")
-    if data["pca"].get("gene_rows") is not None:
-        od = data["pca"]["odgenes"]
-        G_all = len(od["gsf"])
-        if gficf_new.shape[0] != G_all:
-            raise ValueError("gficf_new must have one row per row of data['gficf'] (data['pca']['odgenes'])")
-        rows = np.asarray(data["pca"]["gene_rows"], dtype=np.int64)
-        scale = np.ascontiguousarray(od["gsf"], dtype=np.float64) if data["pca"].get("rescale") else None
-        every = len(rows) == G_all
-        if scale is not None or not every:
-            gficf_new = select_scale_rows(gficf_new, None if every else rows, scale, ctx)
+    if data["pca"].get("type") == "NMF":
+        return nmf_project(data, gficf_new, ctx=ctx)
+    gficf_new = _pca_new_rows(data, gficf_new, ctx)
     genes = np.asfortranarray(data["pca"]["genes"], dtype=np.float64)
     M, colptr, rowidx, x = _csc_parts(gficf_new)
     G, n_new = M.shape
@@ -4567,6 +4825,108 @@ class HipOps:
         info = np.zeros(2, dtype=np.int64)
         check(_harmony_lib.load().gficf_harmony_sync(self._bind(), _tptr(ws), _np_ptr(info)))
         return {"zero_rows": int(info[0]), "flat_clusters": int(info[1])}
+
+    # -- NMF (libgficf_nmf.so, include/gficf_nmf.h); dense operands float64, ROW-major with the pitch ``_nmf_lib.ld(k)`` (W: (G, ld),
+    # H as its transpose: (N, ld)), a Gram matrix (lp, lp) with ``_nmf_lib.lp(k)``; colptr int64, rowidx int32, x float64; ``ws``: uint8
+    # of ``nmf_workspace_bytes`` (``_nmf_lib.NNLS_WS_BYTES`` for ``nnls``), its first word zero before the first stage
+    # (``torch.zeros``).  Every stage only enqueues; ``nmf`` waits once an iteration; ``nmf_sync(ws)`` waits and collects the
+    # deferred errors.
+    @staticmethod
+    def nmf_workspace_bytes(G: int, N: int, nnz: int, k: int) -> int:
+        """Device scratch of the ``nmf_*`` stages on a G x N (or N x G) matrix; 0 on sizes every stage refuses."""
+        from . import _nmf_lib
+
+        return int(_nmf_lib.load().gficf_nmf_workspace_bytes(int(G), int(N), int(nnz), int(k)))
+
+    @staticmethod
+    def _nmf_dense(k, **tensors):
+        """Every named tensor (None: not given) is (rows, ld(k)) float64: the stages index them by that pitch."""
+        from . import _nmf_lib
+
+        for name, (t, rows) in tensors.items():
+            if t is not None and (t.dim() != 2 or tuple(t.shape) != (int(rows), _nmf_lib.ld(k)) or t.element_size() != 8):
+                raise ValueError(f"{name} must be a ({int(rows)}, {_nmf_lib.ld(k)}) float64 tensor for k = {k}, not {tuple(t.shape)}")
+
+    @staticmethod
+    def _nmf_small(k, S=None, sweeps=None, rows=0, counts=None, d=None):
+        from . import _nmf_lib
+
+        if S is not None and (S.dim() != 2 or S.shape[0] < _nmf_lib.lp(k) or S.shape[1] != _nmf_lib.lp(k)):
+            raise ValueError(f"S must be ({_nmf_lib.lp(k)}, {_nmf_lib.lp(k)}) for k = {k}")
+        if sweeps is not None and (sweeps.numel() < rows or sweeps.element_size() != 4):
+            raise ValueError(f"sweeps must hold {rows} int32")
+        if counts is not None and (counts.numel() < 2 or counts.element_size() != 8):
+            raise ValueError("counts must hold 2 int64")
+        if d is not None and (d.numel() < k or d.element_size() != 8):
+            raise ValueError(f"d must hold {k} float64")
+
+    def nnls(self, k, S, B, H0, cd_tol, cd_maxit, H, sweeps, ws):
+        """The solve for ``k`` coordinates: S (>= k rows, >= k columns; its row stride is the pitch), B, H0 (or None: from
+        zero), H (M, ld(k)); sweeps int32 of M."""
+        from . import _nmf_lib
+
+        k, M = int(k), int(B.shape[0])
+        if S.dim() != 2 or S.shape[0] < k or S.shape[1] < k or S.element_size() != 8:
+            raise ValueError(f"S must be a float64 matrix of at least {k} x {k}")
+        self._nmf_dense(k, B=(B, M), H0=(H0, M), H=(H, M))
+        self._nmf_small(k, sweeps=sweeps, rows=M)
+        check(_nmf_lib.load().gficf_nnls_device(self._bind(), M, k, _tptr(S), int(S.stride(0)), _tptr(B), _tptr(H0), float(cd_tol), int(cd_maxit),
+                                                _tptr(H), _tptr(sweeps), _tptr(ws), int(ws.numel())))
+
+    def nmf_half(self, n_in, n_out, colptr, rowidx, x, nnz, k, X, Y, d, warm, l1, ridge, cd_tol, cd_maxit, ws, S=None, B=None, sweeps=None,
+                 counts=None):
+        """One half-step on a CSC matrix of n_in rows and n_out columns: X (n_in, ld) -> Y (n_out, ld), d (k), both also read
+        with ``warm``.  Optional outputs: S (lp, lp), B (n_out, ld), sweeps int32 of n_out, counts int64 of 2 (dead, capped)."""
+        from . import _nmf_lib
+
+        self._nmf_dense(k, X=(X, n_in), Y=(Y, n_out), B=(B, n_out))
+        self._nmf_small(k, S=S, sweeps=sweeps, rows=int(n_out), counts=counts, d=d)
+        check(_nmf_lib.load().gficf_nmf_half_device(self._bind(), int(n_in), int(n_out), _tptr(colptr), _tptr(rowidx), _tptr(x), int(nnz), int(k),
+                                                    _tptr(X), _tptr(Y), _tptr(d), 1 if warm else 0, float(l1), float(ridge), float(cd_tol),
+                                                    int(cd_maxit), _tptr(S), _tptr(B), _tptr(sweeps), _tptr(counts), _tptr(ws), int(ws.numel())))
+
+    def nmf_loss(self, G, N, colptr, rowidx, x, nnz, k, W, d, H, loss, ws):
+        """``loss`` (float64 of 4): the loss, ``||A||^2``, the cross term, the quadratic term."""
+        from . import _nmf_lib
+
+        self._nmf_dense(k, W=(W, G), H=(H, N))
+        self._nmf_small(k, d=d)
+        if loss.numel() < 4 or loss.element_size() != 8:
+            raise ValueError("loss must hold 4 float64")
+        check(_nmf_lib.load().gficf_nmf_loss_device(self._bind(), int(G), int(N), _tptr(colptr), _tptr(rowidx), _tptr(x), int(nnz), int(k), _tptr(W),
+                                                    _tptr(d), _tptr(H), _tptr(loss), _tptr(ws), int(ws.numel())))
+
+    def nmf(self, G, N, colptr, rowidx, x, nnz, k, W0, tol, maxit, L1_w, L1_h, ridge, cd_tol, cd_maxit, track_loss, W, d, H, ws) -> dict:
+        """The chain; W0 and W (G, ld) may be the same tensor.  Returns ``delta`` and ``loss`` (per iteration; ``loss`` None unless
+        tracked), ``iterations``, ``converged``, ``dead`` and ``capped_rows``."""
+        from . import _nmf_lib
+
+        maxit = int(maxit)
+        self._nmf_dense(k, W0=(W0, G), W=(W, G), H=(H, N))
+        self._nmf_small(k, d=d)
+        delta, loss, info = np.full(max(maxit, 1), np.nan), np.full(max(maxit, 1), np.nan), np.zeros(4, dtype=np.int64)
+        check(_nmf_lib.load().gficf_nmf_device(self._bind(), int(G), int(N), _tptr(colptr), _tptr(rowidx), _tptr(x), int(nnz), int(k), _tptr(W0),
+                                               float(tol), maxit, float(L1_w), float(L1_h), float(ridge), float(cd_tol), int(cd_maxit),
+                                               1 if track_loss else 0, _tptr(W), _tptr(d), _tptr(H), _np_ptr(delta), _np_ptr(loss), _np_ptr(info),
+                                               _tptr(ws), int(ws.numel())))
+        it = int(info[0])
+        return {"delta": delta[:it], "loss": loss[:it] if track_loss else None, "iterations": it, "converged": bool(info[1]), "dead": int(info[2]),
+                "capped_rows": int(info[3])}
+
+    def nmf_project(self, G, n_new, colptr, rowidx, x, nnz, k, W, ridge, cd_tol, cd_maxit, H, ws, S=None, B=None, sweeps=None):
+        """New cells against W (G, ld): H (n_new, ld); optional outputs as in ``nmf_half``."""
+        from . import _nmf_lib
+
+        self._nmf_dense(k, W=(W, G), H=(H, n_new), B=(B, n_new))
+        self._nmf_small(k, S=S, sweeps=sweeps, rows=int(n_new))
+        check(_nmf_lib.load().gficf_nmf_project_device(self._bind(), int(G), int(n_new), _tptr(colptr), _tptr(rowidx), _tptr(x), int(nnz), int(k),
+                                                       _tptr(W), float(ridge), float(cd_tol), int(cd_maxit), _tptr(H), _tptr(S), _tptr(B),
+                                                       _tptr(sweeps), _tptr(ws), int(ws.numel())))
+
+    def nmf_sync(self, ws):
+        from . import _nmf_lib
+
+        check(_nmf_lib.load().gficf_nmf_sync(self._bind(), _tptr(ws)))
 
     # -- overdispersed genes (libgficf_od.so); ``ws``: uint8 of ``od_workspace_bytes``, its first word zero before the first stage
     # (``torch.zeros``); ``od_fit`` and ``od_bh_log`` wait once for their host stage, the others only enqueue; ``od_sync(ws)``
